@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — Mreads/s of the k-mer query hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|light|tiny] [--mode read|db]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|light|tiny] [--mode read|db] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line (value, ms_per_step, workload, table).  Everything else below -
+roofline, known answer, cpu_baseline and the extra legs - is measured with --full.  --dump-outputs DIR writes the result rows of
+the last timed step for a fixed, seeded sample of reads (DIR/results.npy, float64; DIR/read_index.npy).
 
 A "step" = one pass of the hot path (fused query kernel: canonical k-mer extraction + bucketed probe + per-read
 per-target hit counts + best/second) over one batch of synthetic reads that is already resident in HBM.
@@ -641,7 +645,19 @@ def main():
                     help="N > 1, read mode: seconds after which the line is printed without the table-sharded extra leg")
     ap.add_argument("--no-db-leg", action="store_true",
                     help="N > 1, read mode: skip the extra table-sharded measurement reported as \"table_sharded\"")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline, known answer, results digest, cpu_baseline and the extra legs "
+                         "(pipeline, table_sharded_proxy, two_strand_table, cross_layouts, end_to_end, table_sharded); the --no-* "
+                         "flags and --time-budget act on these.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the result rows of the last step (MIC_RESULT_WORDS u32 per read, as float64) "
+                         "of a fixed, seeded sample of reads to DIR/results.npy and the sampled read indices to DIR/read_index.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if not args.full:
+        args.no_cpu = args.no_pipeline = args.no_e2e = args.no_parts_proxy = args.no_default_layout = args.no_db_leg = True
+        args.cross_layouts = ""
     t_main0 = time.time()
     skipped_legs, cut_off_legs = [], []
 
@@ -871,17 +887,72 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    kernel_ms = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-        if args.steps <= 64:
-            pass
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    crowd_stats = eng.last_crowd_stats() if not db_mode else None
+    flagged = n_flagged[0]
+    ms_per_step = elapsed / args.steps * 1e3
+    total_reads = n_reads * (world if args.mode == "read" else 1)
+    value = total_reads / (elapsed / args.steps) / 1e6
+
+    if args.dump_outputs:
+        # the rows a caller of the timed path receives after the last step (db mode: gathered over the group, in read order), for a
+        # fixed sample of reads: the same reads in every run with the same arguments, so that two builds compare row for row
+        res_all = sp.gather() if db_mode else d_res
+        if rank == 0:
+            n_rows = res_all.shape[0]
+            n_dump = min(n_rows, 1 << 19)                   # 2^19 rows x 8 words x 8 bytes = 32 MB, + 4 MB of indices
+            pick = np.sort(np.random.default_rng(20261016).choice(n_rows, n_dump, replace=False))
+            rows = res_all[torch.from_numpy(pick).to(dev)].cpu().numpy().view(np.uint32)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "results.npy"), rows.astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, "read_index.npy"), pick.astype(np.float64))
+            log(f"bench.py: result rows of {n_dump} of {n_rows} reads written to {args.dump_outputs}")
+        del res_all
+
+    def headline():
+        """the line's fields that a plain run prints too: the timed steps, the workload and the table they ran on"""
+        reads_label = f"{n_reads / 1e6:g}M" + (" per GPU" if world > 1 and args.mode == "read" else "")
+        return {
+            "metric": f"Mreads/sec ({reads_label} x {'2x' if paired else ''}{read_len}bp{' pairs' if paired else ''}, k={k})", "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "strong" if db_mode else "weak", "vs_baseline": None, "dtype": "u64",
+            "data": "synthetic", "full": args.full,
+            "config": {"workload": w["name"], "reads_per_gpu": n_reads, "read_len": read_len, "k": k,
+                       "reads_format": "generator's fixed pitch, a 0 behind every read" if args.pitch_layout else
+                                       "the packer's: reads back to back, readsPointer[r + 1] = end of read r (CuCLARK_hh.hh:1616-1716)",
+                       "mode": (f"{P} part(s) x {n_groups} read group(s): " + (PART_MODE[info["layout"]] if P > 1 else "table replicated") +
+                                " + all_to_all of sparse rows" if db_mode else
+                                ("read-sharded, table replicated" if world > 1 else "single GPU, table resident")),
+                       "table": {"htsize": info["htsize"], "kmers": info["n_elems"], "slot_class": info["slot_class"],
+                                 "layout": {1: "direct: one 64-B slot per on-disk bucket", 2: "minimizer-keyed 128-B slots", 3: "super-k-mer 128-B slots",
+                                            4: "super-k-mer 128-B slots, both strands stored (no reverse complement in the query)"}[info["layout"]],
+                                 "minimizer_len": info["minimizer_len"], "largest_minimizer_bucket": info["max_chain"],
+                                 "hbm_GB": round(info["hbm_bytes"] / 1e9, 2), "overflow_slots": info["n_overflow"],
+                                 "max_bucket": info["max_bucket"], "on_disk_equiv_GB": round((info["htsize"] + n_el * (w["key_bytes"] + 2)) / 1e9, 2)},
+                       "flagged_reads_dense_path": flagged,
+                       "setup_s": {"synth_db": round(t_gen, 1), "table_build": round(t_build, 1), "table_build_stages": build_stages},
+                       "library": lib_id}}
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # mean duration of the query kernel alone (HIP events recorded around it on its own stream), sampled
     # outside the timed loop so the event reads do not serialise it
+    kernel_ms = []
     q_first, q_n = (sp.first, sp.n) if db_mode else (0, n_reads)       # the reads this rank's kernel sees in one pass
     for _ in range(min(args.steps, 5)):
         if db_mode:      # the pass launches the kernel per chunk: time ONE launch over all of this rank's reads instead
@@ -890,17 +961,8 @@ def main():
             step()
         kernel_ms.append(eng.last_query_ms())
     torch.cuda.synchronize()
-    if use_dist:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    crowd_stats = eng.last_crowd_stats() if not db_mode else None
-    ms_per_step = elapsed / args.steps * 1e3
-    total_reads = n_reads * (world if args.mode == "read" else 1)
-    value = total_reads / (elapsed / args.steps) / 1e6
 
     # ---- bookkeeping for the roofline: measured k-mers, hit rate, probed-bucket length (product-side kernel)
-    flagged = n_flagged[0]
     st = eng.probe_stats_device(d_rp.data_ptr() + 4 * q_first, d_cont.data_ptr(), q_n)
     kern_s = float(np.mean(kernel_ms)) / 1e3
     h = st["hits"] / max(st["probed"], 1)
@@ -1067,34 +1129,14 @@ def main():
     def _emit_locked(ts):
         pipeline, e2e, proxy = legs.get("pipeline"), legs.get("end_to_end"), legs.get("table_sharded_proxy")
         two_strand, cross = legs.get("two_strand_table"), legs.get("cross_layouts")
-        reads_label = f"{n_reads / 1e6:g}M" + (" per GPU" if world > 1 and args.mode == "read" else "")
-        out = {
-            "metric": f"Mreads/sec ({reads_label} x {'2x' if paired else ''}{read_len}bp{' pairs' if paired else ''}, k={k})", "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "strong" if db_mode else "weak", "vs_baseline": None, "dtype": "u64",
-            "data": "synthetic",
-            "config": {"workload": w["name"], "reads_per_gpu": n_reads, "read_len": read_len, "k": k,
-                       "reads_format": "generator's fixed pitch, a 0 behind every read" if args.pitch_layout else
-                                       "the packer's: reads back to back, readsPointer[r + 1] = end of read r (CuCLARK_hh.hh:1616-1716)",
-                       "mode": (f"{P} part(s) x {n_groups} read group(s): " + (PART_MODE[info["layout"]] if P > 1 else "table replicated") +
-                                " + all_to_all of sparse rows" if db_mode else
-                                ("read-sharded, table replicated" if world > 1 else "single GPU, table resident")),
-                       "table": {"htsize": info["htsize"], "kmers": info["n_elems"], "slot_class": info["slot_class"],
-                                 "layout": {1: "direct: one 64-B slot per on-disk bucket", 2: "minimizer-keyed 128-B slots", 3: "super-k-mer 128-B slots",
-                                            4: "super-k-mer 128-B slots, both strands stored (no reverse complement in the query)"}[info["layout"]],
-                                 "minimizer_len": info["minimizer_len"], "largest_minimizer_bucket": info["max_chain"],
-                                 "hbm_GB": round(info["hbm_bytes"] / 1e9, 2), "overflow_slots": info["n_overflow"],
-                                 "max_bucket": info["max_bucket"], "on_disk_equiv_GB": round((info["htsize"] + n_el * (key_b + 2)) / 1e9, 2)},
-                       "flagged_reads_dense_path": flagged, "results_sha256_16": results_digest,
-                       "crowded": (None if crowd_stats is None else
-                                   {"side_table_kmers": info["side_kmers"], "reads_with_crowded_runs": crowd_stats["reads"], "crowded_runs": crowd_stats["runs"],
-                                    "reads_to_dense_path_for_lack_of_room": crowd_stats["reads_to_dense_path"],
-                                    "what": "reads that met a crowded minimizer (microsatellites: one minimizer in thousands of contexts, its k-mers in a side "
-                                            "table) are finished by crowd_finish_kernel behind the query kernel, inside the timed step"}),
-                       "setup_s": {"synth_db": round(t_gen, 1), "table_build": round(t_build, 1), "table_build_stages": build_stages},
-                       "library": lib_id},
-            "roofline": roofline, "cpu_baseline": cpu, "known_answer": known,
-        }
+        out = headline()
+        out["config"]["results_sha256_16"] = results_digest
+        out["config"]["crowded"] = (None if crowd_stats is None else
+                                    {"side_table_kmers": info["side_kmers"], "reads_with_crowded_runs": crowd_stats["reads"], "crowded_runs": crowd_stats["runs"],
+                                     "reads_to_dense_path_for_lack_of_room": crowd_stats["reads_to_dense_path"],
+                                     "what": "reads that met a crowded minimizer (microsatellites: one minimizer in thousands of contexts, its k-mers in a side "
+                                             "table) are finished by crowd_finish_kernel behind the query kernel, inside the timed step"})
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "known_answer": known})
         if pipeline is not None:
             out["pipeline"] = pipeline
         if e2e is not None:
@@ -1186,7 +1228,7 @@ def main():
             Rows are compared by their digest."""
             import subprocess
             t0 = time.time()
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--layout", name, "--steps", str(steps), "--warmup", "2", "--no-cpu",
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--layout", name, "--steps", str(steps), "--warmup", "2", "--full", "--no-cpu",
                    "--no-pipeline", "--no-e2e", "--no-parts-proxy", "--no-two-strand", "--reads", str(n_reads), "--read-len", str(args.read_len),
                    "--time-budget", "100000"]
             if args.pitch_layout:

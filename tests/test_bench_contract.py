@@ -11,7 +11,7 @@ import golden_util as gu
 
 @pytest.mark.gpu
 def test_bench_tiny_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -50,7 +50,7 @@ def test_bench_tiny_json_contract():
 
 
 def _bench(*args, timeout=1500):
-    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--full", *args], capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -150,6 +150,39 @@ def test_bench_light27_config2_proper():
     assert "k=27" in d["metric"]
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_steps_rows(tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes the result rows of the last timed step (tiny: all
+    100 000 reads, so the rows must be the very rows the --full run digests and checks), the same in every run."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(plain)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "Mreads/s"
+    assert abs(d["value"] - d["config"]["reads_per_gpu"] / d["ms_per_step"] / 1e3) / d["value"] < 0.02
+    for key in ("roofline", "cpu_baseline", "known_answer", "pipeline", "end_to_end", "two_strand_table"):
+        assert key not in d, key
+    d2 = _bench("--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-pipeline", "--no-e2e", "--no-parts-proxy", "--no-default-layout",
+                "--dump-outputs", str(full))
+    assert d2["full"] is True and d2["known_answer"]["label_and_count_ok"] == 1.0
+    import hashlib
+    import numpy as np
+    rows, idx = np.load(plain / "results.npy"), np.load(plain / "read_index.npy")
+    assert rows.dtype == np.float64 and rows.shape == (100_000, 8) and (idx == np.arange(100_000)).all()
+    assert (rows == np.load(full / "results.npy")).all()
+    assert hashlib.sha256(np.ascontiguousarray(rows[:, :5].astype(np.uint32)).tobytes()).hexdigest()[:16] == d2["config"]["results_sha256_16"]
+
+
+def test_bench_has_the_full_and_dump_outputs_options():
+    r = subprocess.run([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-1000:]
+
+
 def test_bench_has_the_contract_flags():
     src = open(os.path.join(gu.ROOT, "bench.py")).read()
     for flag in ("--gpus", "--steps", "--warmup"):
@@ -179,7 +212,7 @@ def test_bench_two_ranks_on_one_gpu(mode):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _run_ranks([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                     "127.0.0.1", "--master-port", "29533", os.path.join(gu.ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                    "--warmup", "1", "--workload", "tiny", "--mode", mode[:2] if mode != "read" else mode, "--backend", "gloo",
+                    "--warmup", "1", "--workload", "tiny", "--mode", mode[:2] if mode != "read" else mode, "--backend", "gloo", "--full",
                     *(["--parts", "1"] if mode == "db_2d" else [])], env, port=29533)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -209,7 +242,7 @@ def test_bench_line_stands_when_the_table_sharded_leg_does_not_finish():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _run_ranks([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                     "127.0.0.1", "--master-port", "29541", os.path.join(gu.ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                    "--warmup", "1", "--workload", "tiny", "--mode", "read", "--backend", "gloo", "--db-leg-timeout", "0.001"], env, port=29541)
+                    "--warmup", "1", "--workload", "tiny", "--mode", "read", "--backend", "gloo", "--full", "--db-leg-timeout", "0.001"], env, port=29541)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -225,7 +258,7 @@ def test_bench_four_ranks_two_dimensional_layout():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _run_ranks([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
                     "127.0.0.1", "--master-port", "29537", os.path.join(gu.ROOT, "bench.py"), "--gpus", "4", "--steps", "2",
-                    "--warmup", "1", "--workload", "tiny", "--mode", "read", "--backend", "gloo"], env, port=29537)
+                    "--warmup", "1", "--workload", "tiny", "--mode", "read", "--backend", "gloo", "--full"], env, port=29537)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 4 and d["scaling"] == "weak"
@@ -244,7 +277,7 @@ def test_bench_gpus_2_starts_its_two_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = _run_ranks([sys.executable, os.path.join(gu.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny",
-                    "--backend", "gloo", "--no-db-leg"], env)
+                    "--backend", "gloo", "--full", "--no-db-leg"], env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -8,7 +8,7 @@ import pytest
 
 import golden_util as gu
 
-DRIVER = os.path.join(gu.ROOT, "integration", "_bin", "shim_driver")
+DRIVER = os.path.join(gu.ROOT, "oracle", "_ref", "shim_driver")      # (oracle/Makefile, target shim: built with the reference binaries)
 
 
 def test_shim_matches_the_documented_text():
@@ -27,7 +27,7 @@ def test_shim_compiles_against_reference_types(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.access(DRIVER, os.X_OK), reason="integration/_bin/shim_driver not built")
+@pytest.mark.skipif(not os.access(DRIVER, os.X_OK), reason="oracle/_ref/shim_driver not built")
 def test_shim_drives_the_engine_like_cuclark(tmp_path):
     from cuclark_amd import host
     prefix, meta = gu.materialize_db("light_k27_u32", str(tmp_path))
@@ -59,7 +59,7 @@ def test_shim_drives_the_engine_like_cuclark(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.access(DRIVER, os.X_OK), reason="integration/_bin/shim_driver not built")
+@pytest.mark.skipif(not os.access(DRIVER, os.X_OK), reason="oracle/_ref/shim_driver not built")
 def test_shim_completes_a_read_of_80_targets_exactly_on_three_engines(tmp_path):
     """a read whose row does not fit (80 targets, MAXHITS = 15) through the shim on three engines (numDevices = 3:
     parts of the table, ONE upload fanned out by mic_batch_query_group, rows summed by mic_batch_merge_shards).  Sum / best /

@@ -14,7 +14,8 @@ for item in $VARS; do
     echo "variant $x: counters" >> $R/gpurun_out/abl/progress.txt
     timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $R/gpurun_out/abl/p_$x -- python3 $R/bench.py --allow-variant-lib --no-parts-proxy --no-two-strand --no-cpu --no-pipeline --no-e2e --steps 3 --warmup 1 "$@" > $R/gpurun_out/abl/bench_$x.json 2> $R/gpurun_out/abl/err_$x.txt
     echo "variant $x: timing" >> $R/gpurun_out/abl/progress.txt
-    timeout -k 10 200 python3 $R/bench.py --allow-variant-lib --no-parts-proxy --no-two-strand --no-cpu --no-pipeline --no-e2e --steps 10 --warmup 3 "$@" > $R/gpurun_out/abl/time_$x.json 2>> $R/gpurun_out/abl/err_$x.txt )
+    A=${MIC_LIB_PATH%/*}          # (the folder the variant library was copied to: the run's outputs)
+    timeout -k 10 200 python3 $R/bench.py --full --allow-variant-lib --no-parts-proxy --no-two-strand --no-cpu --no-pipeline --no-e2e --steps 10 --warmup 3 "$@" > $A/time_$x.json 2>> $A/err_$x.txt )
   python3 - <<PY
 import csv, glob, collections, json
 agg = collections.defaultdict(list)

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=${1:-$R/gpurun_out/r5}
 mkdir -p "$OUT"
-MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 python3 "$R/bench.py" --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline \
+MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline \
   > "$OUT/cli_wall_bench.json" 2> "$OUT/cli_wall_bench.err"
 D=$(grep -o "files kept in .*" "$OUT/cli_wall_bench.err" | awk '{print $4}')
 echo "files in $D"

@@ -15,10 +15,10 @@ b)
     OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
     EXTRA=""; [ "$ENVV" = "MIC_SINGLE_PART=8" ] && EXTRA="--single-part 8" || export $ENVV
     ( cd /tmp && export TMPDIR=/tmp
-      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 10 --warmup 3 $EXTRA > $OUT/kt_bench.json 2> $OUT/kt.err
+      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --full --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 10 --warmup 3 $EXTRA > $OUT/kt_bench.json 2> $OUT/kt.err
       for pmc in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD" "SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM GRBM_GUI_ACTIVE" "SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_SCA"; do
         name=$(echo $pmc | tr ' ' '_' | cut -c1-40)
-        rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/pmc_$name -- python3 $R/bench.py --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 3 --warmup 1 $EXTRA > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
+        rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/pmc_$name -- python3 $R/bench.py --full --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 3 --warmup 1 $EXTRA > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
       done )
     unset MIC_LAYOUT
     # the 128-byte-slot calibration of FETCH_SIZE is the headline run's (stage a); summarize_profile.py falls back to scale 2

@@ -11,11 +11,11 @@ prof() {   # prof <tag> <bench args...>
   TAG=$1; shift
   OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
   ( cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 20 --warmup 3 "$@" > $OUT/kt_bench.json 2> $OUT/kt.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --full --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 20 --warmup 3 "$@" > $OUT/kt_bench.json 2> $OUT/kt.err
     echo "$TAG kernel trace done"
     for pmc in "${PMCS[@]}"; do
       name=$(echo $pmc | tr ' ' '_' | cut -c1-40)
-      rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/pmc_$name -- python3 $R/bench.py --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 3 --warmup 1 "$@" > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
+      rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/pmc_$name -- python3 $R/bench.py --full --no-parts-proxy --no-default-layout --no-cpu --no-pipeline --no-e2e --steps 3 --warmup 1 "$@" > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
       echo "$TAG pmc $name done"
     done )
 }
@@ -30,7 +30,7 @@ s) prof r06a
 d) prof r06s --layout super2 ;;
 cli)
   OUT=$R/gpurun_out/prof_r06cli; mkdir -p $OUT
-  MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 python3 $R/bench.py --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline --time-budget 100000 > $OUT/bench.json 2> $OUT/bench.err
+  MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 python3 $R/bench.py --full --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline --time-budget 100000 > $OUT/bench.json 2> $OUT/bench.err
   D=$(grep -o "files kept in .*" $OUT/bench.err | awk '{print $4}')
   sleep 30
   ( cd /tmp && export TMPDIR=/tmp

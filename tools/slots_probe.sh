@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 OUT=$R/gpurun_out/slots_probe; mkdir -p $OUT
-MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 timeout -k 10 400 python3 $R/bench.py --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline --time-budget 100000 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+MIC_BENCH_KEEP=1 MIC_BENCH_NO_FASTA=1 timeout -k 10 400 python3 $R/bench.py --full --steps 2 --warmup 1 --no-multi-engine --no-parts-proxy --no-default-layout --e2e-reps 1 --no-cpu --no-pipeline --time-budget 100000 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 D=$(grep -o "files kept in .*" $OUT/bench.err | awk '{print $4}')
 CMD="$R/exe/cuCLARK -k 31 --htsize 1610612741 -T $D/targets.txt -D $D/DB -O $D/reads_1.fq -R $D/out_p -n 12"
 for MB in ${@:-64 128}; do

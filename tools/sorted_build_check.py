@@ -43,7 +43,7 @@ if __name__ == "__main__":
     n = sys.argv[1] if len(sys.argv) > 1 else "0"
     if int(n) > 0:
         for mode, env in (("classic", {"MIC_S_CLASSIC": "1"}), ("sorted", {})):
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "light27", "--layout", "super", "--steps", "2", "--warmup", "1", "--no-cpu",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "light27", "--layout", "super", "--steps", "2", "--warmup", "1", "--no-cpu",
                                 "--no-pipeline", "--no-e2e", "--no-parts-proxy", "--no-default-layout"], env=dict(os.environ, MIC_LOAD_TIMING="1", **env),
                                capture_output=True, text=True)
             print(mode, "bench exit", r.returncode)
