@@ -54,6 +54,11 @@ class MicIngestResult(C.Structure):
 
 MIC_INGEST_OK, MIC_INGEST_FALLBACK, MIC_INGEST_ODD_RECORD, MIC_INGEST_TRUNCATED = 0, 1, 2, 4
 MIC_INGEST_LONG_READ, MIC_INGEST_TOO_MANY, MIC_INGEST_DENSE = 8, 16, 32
+MIC_INGEST_NO_CSV = 16          # ingest flag (not a status bit): no CSV kernels, no text back
+
+
+class MicAbundFilter(C.Structure):
+    _fields_ = [("conf_num", C.c_uint64), ("conf_den", C.c_uint64), ("gamma_num", C.c_uint64), ("gamma_den", C.c_uint64)]
 
 # every symbol include/mi_clark.h declares: (name, restype, argtypes)
 _VP, _SZ, _U32P, _U16P, _U64P = C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p
@@ -125,6 +130,12 @@ SYMBOLS = [
     ("mic_text_copy", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, _VP, _SZ, C.POINTER(_SZ)]),
     ("mic_text_free", C.c_int, [_VP, _VP]),
     ("mic_text_format", C.c_int, [_VP]),
+    ("mic_abundance_start", C.c_int, [_VP, C.POINTER(MicAbundFilter)]),
+    ("mic_abundance_fetch", C.c_int, [_VP, _VP, _SZ]),
+    ("mic_abundance_stop", C.c_int, [_VP]),
+    ("mic_abundance_device", C.c_int, [_VP, _VP, _VP, _SZ, C.POINTER(MicAbundFilter), _VP, _VP]),
+    ("mic_abundance_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, C.POINTER(MicAbundFilter), _VP]),
+    ("mic_abund_parse", C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("mic_format_ratio_g", C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p]),
     ("mic_key_bytes_rule", C.c_int, [C.c_uint64, C.c_int]),
     ("mic_index_reads", C.c_long, [_VP, _SZ, _SZ, _U64P, _U64P, _U64P, _U64P, _U64P]),

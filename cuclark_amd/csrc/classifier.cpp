@@ -236,6 +236,34 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
   }
 }
 
+void Classifier::reset_counts() {
+  if (!counting()) return;
+  for (mic_engine* e : engines_) check(mic_abundance_start(e, &opt_.abund_filter), "abundance counters");
+  std::lock_guard<std::mutex> lk(count_mu_);
+  host_counts_.assign(names_.size() + 2, 0);
+}
+
+// a batch the host path classified (results: MIC_RESULT_WORDS per read, norm: the Length column of each read)
+void Classifier::count_host(const std::vector<uint32_t>& results, const std::vector<uint32_t>& norm) {
+  std::vector<uint64_t> c(names_.size() + 2, 0);
+  check(mic_abundance_host(results.data(), norm.data(), norm.size(), (int)opt_.k, (uint32_t)names_.size(), &opt_.abund_filter, c.data()),
+        "abundance (host path)");
+  std::lock_guard<std::mutex> lk(count_mu_);
+  if (host_counts_.size() != c.size()) host_counts_.assign(c.size(), 0);
+  for (size_t i = 0; i < c.size(); ++i) host_counts_[i] += c[i];
+}
+
+std::vector<uint64_t> Classifier::abundance_counts() {
+  std::vector<uint64_t> total(names_.size() + 2, 0), part(names_.size() + 2);
+  for (mic_engine* e : engines_) {
+    check(mic_abundance_fetch(e, part.data(), part.size()), "abundance counters");
+    for (size_t i = 0; i < part.size(); ++i) total[i] += part[i];
+  }
+  std::lock_guard<std::mutex> lk(count_mu_);
+  for (size_t i = 0; i < host_counts_.size() && i < total.size(); ++i) total[i] += host_counts_[i];
+  return total;
+}
+
 Classifier::~Classifier() {
   release_ingest();
   for (mic_engine* e : engines_) mic_destroy(e);
@@ -378,6 +406,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
     return;
   }
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
+  if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   std::ifstream o_fd(objects), r_fd(results);
   std::string o_line, r_line;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;
@@ -456,6 +485,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
     list_mode = !((!line.empty() && (line[0] == '>' || line[0] == '@')) || ele.size() == 2);
   }
   if (!list_mode) { one(f1, f2, results, false); return; }
+  if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   std::ifstream o1(f1), o2(f2), r_fd(results);
   std::string a, b, r;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;

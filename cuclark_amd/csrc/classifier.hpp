@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -30,7 +31,9 @@ struct Options {
   bool db_sharded = false;    // --db-sharded: the devices hold parts of the table (the reference's -d mode), see Classifier's ctor
   size_t parts = 0;           // --parts P: parts the table is cut into under --db-sharded (0 = the smallest number whose part fits a device)
   uint64_t htsize = 1610612741ull;  // parameters.hh:39 / parameters_light_hh:40; --htsize overrides
-  std::string targets, folder, objects, objects2, results;
+  std::string targets, folder, objects, objects2, results;   // results empty: no result CSV (a summary-only --abundance run)
+  std::string abundance;                                     // --abundance <file>: the abundance profile is counted (mic_abundance_*)
+  mic_abund_filter abund_filter = {5, 10, 0, 1};             // --min-confidence / --min-gamma / --highconfidence (CLARK's -c 0.5 -g 0)
 };
 
 class Classifier {
@@ -79,6 +82,10 @@ class Classifier {
   };
   bool run_stream(Feeder& f, const std::string& results_base, bool paired, size_t total_bytes);   // false: feeder gave up, nothing written
 
+  // --abundance: reads per bucket of the run (include/mi_clark.h: [0] unassigned, [1] filtered out, [t + 2] target t), the device
+  // counters of all engines plus what the host path counted
+  std::vector<uint64_t> abundance_counts();
+
   std::string db_name() const;  // getdbName, CuCLARK_hh.hh:580-591
   const std::vector<std::string>& target_names() const { return names_; }
 
@@ -107,6 +114,13 @@ class Classifier {
   size_t parts_ = 1, groups_ = 1;
   bool gz_on_device_ = true;                  // compressed input is inflated on the first engine's device (needs peer access from the others)
   std::atomic<size_t> n_objects_{0};
+  // --abundance: every run over the input starts the counters afresh (a run the feeder gives up is repeated from the start)
+  bool counting() const { return !opt_.abundance.empty(); }
+  void reset_counts();
+  void count_host(const std::vector<uint32_t>& results, const std::vector<uint32_t>& norm);
+  std::vector<uint64_t> host_counts_;
+  std::mutex count_mu_;
+  bool csv_out_ = true;                       // the current run writes a result CSV (false: summary-only --abundance run)
   double prelude_s_ = 0;                      // seconds spent inflating a compressed input before the streaming path started
 };
 

@@ -36,12 +36,14 @@ void Classifier::ensure_batches(size_t max_reads, size_t max_cont) {
 
 void Classifier::run_segments(SegmentSource& src, const std::string& results_base, bool paired) {
   const std::string csv = results_base + ".csv";  // CuCLARK_hh.hh:539-540
-  FILE* fout = fopen(csv.c_str(), "w");
-  if (!fout) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return; }
+  csv_out_ = !results_base.empty();               // (no -R: a summary-only --abundance run writes no result CSV)
+  FILE* fout = csv_out_ ? fopen(csv.c_str(), "w") : nullptr;
+  if (csv_out_ && !fout) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return; }
+  reset_counts();
   struct timeval t0, t1;
   gettimeofday(&t0, nullptr);
   n_objects_ = 0;
-  {  // header (CuCLARK_hh.hh:1957-1972)
+  if (fout) {  // header (CuCLARK_hh.hh:1957-1972)
     std::vector<const char*> nm(names_.size());
     size_t cap = 256;
     for (size_t t = 0; t < names_.size(); ++t) { nm[t] = names_[t].c_str(); cap += names_[t].size() + 2; }
@@ -69,15 +71,15 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
     have = have_next;
   }
   // a full disk shows here at the latest (the command line leaves through _exit: nothing later would flush or report it)
-  const bool write_failed = ferror(fout) != 0;
-  if (fclose(fout) != 0 || write_failed) { if (err.empty()) err = "cannot write " + csv + " (disk full?)"; }
+  const bool write_failed = fout && ferror(fout) != 0;
+  if (fout && (fclose(fout) != 0 || write_failed)) { if (err.empty()) err = "cannot write " + csv + " (disk full?)"; }
   release_batches();
   if (!err.empty()) die(err);
   gettimeofday(&t1, nullptr);
   const double diff = (t1.tv_sec - t0.tv_sec) + (t1.tv_usec - t0.tv_usec) / 1000000.0;
   std::cout << " - Assignment time: " << diff << " s. Speed: ";  // CuCLARK_hh.hh:1938-1944
   std::cout << (size_t)(((double)n_objects_) / (diff) * 60.0) << " objects/min. (" << n_objects_ << " objects)." << std::endl;
-  std::cout << " - Results stored in " << csv << std::endl;
+  if (csv_out_) std::cout << " - Results stored in " << csv << std::endl;
 }
 
 size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, FILE* fout) {
@@ -179,9 +181,12 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       }
       tick(t_query);
       std::string& s = out[b];
-      s.reserve(cnt * (opt_.extended ? 64 + 3 * (size_t)T : 72));
+      const bool emit = csv_out_;
+      if (emit) s.reserve(cnt * (opt_.extended ? 64 + 3 * (size_t)T : 72));
       std::vector<char> line(line_cap);
       std::vector<uint32_t> dense;
+      std::vector<uint32_t> ab_res, ab_norm;        // --abundance: the batch's result rows as the CSV shows them, and the Length column
+      if (counting()) { ab_res.resize(cnt * MIC_RESULT_WORDS); ab_norm.resize(cnt); }
       const uint32_t* res = L.results + lb * slot_reads_ * MIC_RESULT_WORDS;
       const uint32_t* rows = L.rows ? L.rows + lb * slot_reads_ * row_words : nullptr;
       for (size_t i = 0; i < cnt; ++i) {
@@ -216,11 +221,17 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
           }
           dn = dense.data();
         }
+        if (counting()) {
+          memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
+          ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
+        }
+        if (!emit) continue;
         int w = mic_csv_line(line.data(), line.size(), map + name_s[r], (size_t)(name_e[r] - name_s[r]), length[r], paired ? 1 : 0,
                              k, rr, nm.data(), T, opt_.extended ? 1 : 0, row, dn);
         if (w < 0) die("CSV line too long");
         s.append(line.data(), (size_t)w);
       }
+      if (counting()) count_host(ab_res, ab_norm);
     } catch (const std::exception& ex) {
       std::lock_guard<std::mutex> lk(wmu);
       if (err.empty()) err = ex.what();
@@ -230,7 +241,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
     ready[b] = 1;
     while (next_write < nb_total && ready[next_write]) {
       if (sink_) sink_->append(out[next_write]);
-      else if (fwrite(out[next_write].data(), 1, out[next_write].size(), fout) != out[next_write].size() && err.empty()) err = "short write to the result file (disk full?)";
+      else if (fout && fwrite(out[next_write].data(), 1, out[next_write].size(), fout) != out[next_write].size() && err.empty()) err = "short write to the result file (disk full?)";
       std::string().swap(out[next_write]);
       ++next_write;
     }

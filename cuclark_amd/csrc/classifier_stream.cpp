@@ -201,11 +201,18 @@ double strip_fastq_loaders_rate(const std::string& path, size_t chunk, unsigned 
 
 bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool paired, size_t total_bytes) {
   const std::string csv = results_base + ".csv";  // CuCLARK_hh.hh:539-540
+  // no -R (a summary-only --abundance run): no result CSV, the batches go to the device with MIC_INGEST_NO_CSV, no writer thread
+  csv_out_ = !results_base.empty();
+  const bool summary = !csv_out_;
   // a fresh file, not a truncated one: ext4 writes a truncated-and-rewritten file's blocks out when it is closed
   // (auto_da_alloc), 60 ms for the CSV of 16 M reads
-  unlink(csv.c_str());
-  const int out_fd = open(csv.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
-  if (out_fd == -1) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return true; }
+  int out_fd = -1;
+  if (!summary) {
+    unlink(csv.c_str());
+    out_fd = open(csv.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    if (out_fd == -1) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return true; }
+  }
+  reset_counts();
   struct timeval t0, t1;
   gettimeofday(&t0, nullptr);
   // The CSV's blocks are allocated up front (a quarter of the input's size: 42 bytes of CSV per ~165 - 330 bytes of record; cut
@@ -215,14 +222,14 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   // (MIC_CSV_DISCARD: 45-49 ms).  A file system that refuses the call is written as before; MIC_CSV_FALLOCATE=0 turns it off.
   uint64_t prealloc = total_bytes < ((size_t)1 << 40) ? std::min<uint64_t>((uint64_t)total_bytes / 4, (uint64_t)16 << 30) : 0;
   if (const char* env = getenv("MIC_CSV_FALLOCATE")) { long v = atol(env); prealloc = v > 0 && total_bytes < ((size_t)1 << 40) ? (uint64_t)total_bytes / 100 * (uint64_t)v : 0; }
-  if (prealloc < ((uint64_t)1 << 20) || fallocate(out_fd, 0, 0, (off_t)prealloc) != 0) prealloc = 0;
+  if (summary || prealloc < ((uint64_t)1 << 20) || fallocate(out_fd, 0, 0, (off_t)prealloc) != 0) prealloc = 0;
   ensure_ingest(total_bytes);          // inside the timed region, like the reference's CuClarkDB::malloc (CuCLARK_hh.hh:1600-1606)
   std::atomic<uint64_t> ts_first_loaded{0}, ts_last_loaded{0}, ts_last_dev{0}, ts_alloc{0}, ts_last_write{0}, us_write_max{0};   // MIC_CLI_TIMING: stage ends since t0
   const uint64_t t0_us = (uint64_t)t0.tv_sec * 1000000u + (uint64_t)t0.tv_usec;
   { struct timeval t; gettimeofday(&t, nullptr); ts_alloc = (uint64_t)t.tv_sec * 1000000u + (uint64_t)t.tv_usec; }
   n_objects_ = 0;
   uint64_t out_off = 0;
-  {  // header (CuCLARK_hh.hh:1957-1972)
+  if (!summary) {  // header (CuCLARK_hh.hh:1957-1972)
     std::vector<const char*> nm(names_.size());
     for (size_t t = 0; t < names_.size(); ++t) nm[t] = names_[t].c_str();
     char hb[512];
@@ -248,6 +255,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   if (const char* env = getenv("MIC_INGEST_NW")) { long v = atol(env); if (v >= 1 && v <= 32) NW = (size_t)v; }
   size_t NL = T > ND + NW ? T - ND - NW : 1;
   if (S == 1) { ND = NW = NL = 1; }
+  if (summary && S > 1) NL += NW;     // (no writer: its share of the threads loads)
   const bool strip_ok = getenv("MIC_KEEP_QUALITY") == nullptr;
   const bool timing = getenv("MIC_CLI_TIMING") != nullptr;
 
@@ -312,7 +320,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
           break;
         }
         it.id = next_id++;
-        it.flags = (paired ? MIC_INGEST_PAIRED : 0) | (fq ? MIC_INGEST_FASTQ_2LINE : 0);
+        it.flags = (paired ? MIC_INGEST_PAIRED : 0) | (fq ? MIC_INGEST_FASTQ_2LINE : 0) | (summary ? MIC_INGEST_NO_CSV : 0);
       }
       if (trace) it.ts[0] = now_us() - t0_us;
       const uint64_t ta = timing ? now_us() : 0;
@@ -395,6 +403,11 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
       if (trace) it.ts[3] = now_us() - t0_us;
       if (timing) { const uint64_t tn = now_us(); us_dev += tn - ta; ts_last_dev = tn; }
       ++n_batches;
+      if (summary) {             // nothing to write: the slot is free again
+        { std::lock_guard<std::mutex> lk(mu); n_objects_ += it.reads; free_slots.push_back(it.slot); }
+        cv_free.notify_one();
+        continue;
+      }
       {
         std::lock_guard<std::mutex> lk(mu);
         waiting.emplace(it.id, std::move(it));
@@ -448,30 +461,32 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   std::vector<std::thread> th;
   for (size_t i = 0; i < NL; ++i) th.emplace_back(loader);
   for (size_t i = 0; i < ND; ++i) th.emplace_back(device);
-  for (size_t i = 1; i < NW; ++i) th.emplace_back(writer);
-  writer();
+  if (!summary) {
+    for (size_t i = 1; i < NW; ++i) th.emplace_back(writer);
+    writer();
+  }
   const uint64_t tj0 = now_us();
   for (auto& t : th) t.join();
   const uint64_t tj1 = now_us();
   if (prealloc && ftruncate(out_fd, (off_t)out_off) != 0 && err.empty()) err = "Failed to write the results file.";
-  close(out_fd);
+  if (out_fd != -1) close(out_fd);
   const uint64_t tj2 = now_us();
   release_batches();
   const uint64_t tj3 = now_us();
   for (const std::string& ln : trace_lines) std::cerr << ln << "\n";
   if (timing) std::cerr << "[timing] teardown: join " << (tj1 - tj0) / 1e3 << " ms, close " << (tj2 - tj1) / 1e3 << " ms, batch buffers " << (tj3 - tj2) / 1e3 << " ms" << std::endl;
-  if (feed.gave_up()) { unlink(csv.c_str()); return false; }
+  if (feed.gave_up()) { if (!summary) unlink(csv.c_str()); return false; }
   if (!err.empty()) die(err);
   gettimeofday(&t1, nullptr);
   // (the time it took to inflate a compressed input up front belongs to the assignment time)
   const double diff = (t1.tv_sec - t0.tv_sec) + (t1.tv_usec - t0.tv_usec) / 1000000.0 + prelude_s_;
   if (timing) std::cerr << "[timing] device ingest: " << n_batches << " batches of <= " << (cap >> 10) << " KB on " << S
-                        << " slot(s), " << n_fallback << " through the host path; threads: " << NL << " load, " << ND << " device, " << NW
-                        << " write; thread-seconds: load " << us_load / 1e6 << ", device " << us_dev / 1e6 << ", write " << us_write / 1e6
+                        << " slot(s), " << n_fallback << " through the host path; threads: " << NL << " load, " << ND << " device, " << (summary ? 0 : NW)
+                        << " write" << (summary ? " (no result CSV)" : "") << "; thread-seconds: load " << us_load / 1e6 << ", device " << us_dev / 1e6 << ", write " << us_write / 1e6
                         << "; input " << bytes_in / 1e6 << " MB, over the link " << bytes_h2d / 1e6 << " MB; ms since start: slots ready "
                         << (ts_alloc - t0_us) / 1e3 << ", first batch loaded " << (ts_first_loaded - t0_us) / 1e3 << ", last loaded "
-                        << (ts_last_loaded - t0_us) / 1e3 << ", last off the device " << (ts_last_dev - t0_us) / 1e3 << ", last write done " << (ts_last_write - t0_us) / 1e3
-                        << " (longest " << us_write_max / 1e3 << "), end " << diff * 1e3 << std::endl;
+                        << (ts_last_loaded - t0_us) / 1e3 << ", last off the device " << (ts_last_dev - t0_us) / 1e3 << ", last write done "
+                        << (summary ? 0.0 : (ts_last_write - t0_us) / 1e3) << " (longest " << us_write_max / 1e3 << "), end " << diff * 1e3 << std::endl;
   if (timing && parts_ > 1) {
     // MIC_GROUP_TIMING=1: HIP events on every engine's stream around the packed-read fan-out, the query kernel and the row exchange of
     // every batch (mic_ingest_group_stats), summed over the slots' owners
@@ -488,7 +503,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   }
   std::cout << " - Assignment time: " << diff << " s. Speed: ";  // CuCLARK_hh.hh:1938-1944
   std::cout << (size_t)(((double)n_objects_) / (diff) * 60.0) << " objects/min. (" << n_objects_ << " objects)." << std::endl;
-  std::cout << " - Results stored in " << csv << std::endl;
+  if (!summary) std::cout << " - Results stored in " << csv << std::endl;
   return true;
 }
 

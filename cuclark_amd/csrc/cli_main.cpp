@@ -15,7 +15,9 @@
 #include <iterator>
 #include <string>
 
+#include "abundance_table.hpp"
 #include "classifier.hpp"
+#include "mic_abund.h"
 
 #define MAXK 32
 #define SFACTORMAX 30
@@ -50,6 +52,10 @@ static void print_usage(const char* prog) {
                "                     is replicated on every GPU and the batches are dealt to the GPUs\n";
   std::cout << "--parts <P>,         with --db-sharded: number of parts (divides -d; the GPUs form d/P groups that share the reads);\n"
                "                     default: the smallest number of parts that fit a GPU's memory\n";
+  std::cout << "--abundance <file>,  also count the abundance profile of the objects (CLARK's estimate_abundance table) into <file>;\n"
+               "                     without -R no result CSV is written (summary-only run)\n";
+  std::cout << "--min-confidence <c>, --min-gamma <g>, --highconfidence (= --min-confidence 0.75 --min-gamma 0.03), --min-abundance <a>:\n"
+               "                     the filters of the abundance profile (CLARK's -c, -g, --highconfidence, -a; defaults 0.5, 0, 0)\n";
   std::cout << "--tsk, --extended, --light, --htsize <n>, --help, --version\n\n";
 }
 
@@ -138,6 +144,9 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
+  std::string abundance;
+  mic_abund_filter ab_filter = {5, 10, 0, 1};
+  uint64_t ab_min_num = 0, ab_min_den = 1;
 
   for (int i = 1; i < argc; i++) {
     std::string val(argv[i]);
@@ -173,6 +182,19 @@ int main(int argc, char** argv) {
       continue;
     }
     if (val == "--light") { light = true; continue; }
+    if (val == "--abundance") { need("Please specify the file of the abundance profile!"); abundance = argv[i]; continue; }
+    if (val == "--min-confidence" || val == "--min-gamma" || val == "--min-abundance") {
+      need("Please specify the threshold!");
+      const bool a = val == "--min-abundance";
+      uint64_t* num = a ? &ab_min_num : val == "--min-confidence" ? &ab_filter.conf_num : &ab_filter.gamma_num;
+      uint64_t* den = a ? &ab_min_den : val == "--min-confidence" ? &ab_filter.conf_den : &ab_filter.gamma_den;
+      if (!mic_abund_parse_text(argv[i], a ? 100 : 1, num, den)) {
+        std::cerr << "The value of " << val << " should be a decimal number in [0," << (a ? 100 : 1) << "] with at most 9 decimals: " << argv[i] << std::endl;
+        exit(1);
+      }
+      continue;
+    }
+    if (val == "--highconfidence") { ab_filter.conf_num = 75; ab_filter.conf_den = 100; ab_filter.gamma_num = 3; ab_filter.gamma_den = 100; continue; }
     if (val == "--htsize") {
       need("Please specify the table size!");
       htsize_override = strtoull(argv[i], nullptr, 10);
@@ -243,7 +265,11 @@ int main(int argc, char** argv) {
   } else {
     gap = 0;
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || i_results < 0) {
+  if (!abundance.empty() && i_results < 0 && ext) {
+    std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
+    exit(1);
+  }
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty())) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -258,12 +284,23 @@ int main(int argc, char** argv) {
   if (o.folder.empty() || o.folder.back() != '/') o.folder.push_back('/');
   o.objects = argv[i_objects];
   if (i_objects2 > 0) o.objects2 = argv[i_objects2];
-  o.results = argv[i_results];
+  o.results = i_results >= 0 ? argv[i_results] : "";
+  o.abundance = abundance;
+  o.abund_filter = ab_filter;
   mic::Classifier* classifier = nullptr;
   try {
     classifier = new mic::Classifier(o);
     if (i_objects2 > 0) classifier->run_paired(o.objects, o.objects2, o.results);
     else classifier->run(o.objects, o.results);
+    if (!abundance.empty()) {   // the profile, named from the taxonomy set_targets.sh leaves next to the database directory
+      mic::abund::Taxonomy tax;
+      mic::abund::load_taxonomy(o.folder + "../taxonomy", tax);
+      const std::string table = mic::abund::format_table(classifier->abundance_counts(), classifier->target_names(), &tax, ab_min_num, ab_min_den);
+      FILE* f = fopen(abundance.c_str(), "wb");
+      if (!f || fwrite(table.data(), 1, table.size(), f) != table.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the abundance profile: " + abundance);
+      std::cout << " - Abundance profile stored in " << abundance << std::endl;
+    }
   } catch (const std::exception& ex) {
     std::cerr << ex.what() << std::endl;
     delete classifier;

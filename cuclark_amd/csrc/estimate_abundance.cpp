@@ -1,0 +1,160 @@
+// estimate_abundance.cpp — exe/estimate_abundance: CLARK's third step, the abundance profile of one or more result CSVs, on the CPU.
+//   estimate_abundance -F <result.csv> [<result.csv> ...] [-D <database directory>] [-c <conf>] [-g <gamma>] [-a <min %>] [--highconfidence]
+// Plain and --extended result CSVs are read alike (their last seven columns are the same: Length, Gamma, 1st_assignment, score1,
+// 2nd_assignment, score2, confidence); several files are summed.  A read counts for its 1st_assignment when it passes the filter of
+// mic_abund.h: the confidence is decided exactly from score1 and score2, the gamma from the printed Gamma text, compared as a
+// decimal.  The table (abundance_table.hpp) goes to stdout; names and lineages come from <-D>/../taxonomy, the layout set_targets.sh
+// makes, as for exe/cuCLARK --abundance.
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <fstream>
+#include <iostream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "abundance_table.hpp"
+#include "mic_abund.h"
+
+namespace {
+
+[[noreturn]] void usage_exit(const char* msg) {
+  if (msg && *msg) std::cerr << msg << std::endl;
+  std::cerr << "Usage: estimate_abundance -F <result.csv> [<result.csv> ...] [-D <database directory>] [-c <min confidence in [0,1]>]"
+               " [-g <min gamma in [0,1]>] [-a <min abundance in [0,100]>] [--highconfidence]" << std::endl;
+  exit(1);
+}
+
+// value of the printed decimal text >= num / den?  ("%g" forms: "0.762887", "1", "5e-05", "-0"; anything else - "-nan" - is no
+// number and fails every positive threshold)
+bool decimal_at_least(const std::string& s, uint64_t num, uint64_t den) {
+  if (num == 0) return true;
+  size_t i = 0;
+  if (i < s.size() && (s[i] == '-' || s[i] == '+')) { if (s[i] == '-') return false; ++i; }     // (a negative value, or -0)
+  unsigned __int128 m = 0;
+  int exp10 = 0, digits = 0;
+  bool point = false;
+  for (; i < s.size(); ++i) {
+    const char c = s[i];
+    if (c == '.') { if (point) return false; point = true; continue; }
+    if (c < '0' || c > '9') break;
+    ++digits;
+    if (m < (unsigned __int128)1 << 100) { m = m * 10 + (unsigned)(c - '0'); if (point) --exp10; }
+    else if (!point) ++exp10;
+  }
+  if (digits == 0) return false;
+  if (i < s.size()) {
+    if (s[i] != 'e' && s[i] != 'E') return false;
+    ++i;
+    int sign = 1, e = 0;
+    if (i < s.size() && (s[i] == '-' || s[i] == '+')) { if (s[i] == '-') sign = -1; ++i; }
+    if (i >= s.size()) return false;
+    for (; i < s.size(); ++i) { if (s[i] < '0' || s[i] > '9') return false; if (e < 1000) e = e * 10 + (s[i] - '0'); }
+    exp10 += sign * e;
+  }
+  if (m == 0) return false;
+  // m 10^exp10 >= num / den  <=>  m den 10^exp10 >= num
+  unsigned __int128 lhs = m * den, rhs = num;
+  if (exp10 >= 0) { if (exp10 > 12) return true; for (int j = 0; j < exp10; ++j) lhs *= 10; }
+  else {
+    int sh = -exp10;
+    for (; sh > 0 && lhs % 10 == 0; --sh) lhs /= 10;       // (trailing zeros of a long mantissa first: rhs stays in range)
+    if (sh > 26) return false;
+    for (int j = 0; j < sh; ++j) rhs *= 10;
+  }
+  return lhs >= rhs;
+}
+
+bool parse_u32(const std::string& s, uint64_t& v) {
+  if (s.empty() || s.size() > 10) return false;
+  v = 0;
+  for (char c : s) { if (c < '0' || c > '9') return false; v = v * 10 + (uint64_t)(c - '0'); }
+  return v <= 0xFFFFFFFFull;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  std::vector<std::string> files;
+  std::string db;
+  mic_abund_filter f = {5, 10, 0, 1};
+  uint64_t a_num = 0, a_den = 1;
+  for (int i = 1; i < argc; ++i) {
+    const std::string v = argv[i];
+    auto value = [&](const char* what) -> const char* {
+      if (++i >= argc) usage_exit((std::string("Please specify ") + what + ".").c_str());
+      return argv[i];
+    };
+    if (v == "-F") {
+      while (i + 1 < argc && argv[i + 1][0] != '-') files.push_back(argv[++i]);
+      if (files.empty()) usage_exit("Please specify the result file(s).");
+    } else if (v == "-D") {
+      db = value("the database directory");
+    } else if (v == "-c") {
+      const char* t = value("the minimum confidence");
+      if (!mic_abund_parse_text(t, 1, &f.conf_num, &f.conf_den)) usage_exit((std::string("The minimum confidence should be a decimal number in [0,1] (at most 9 decimals): ") + t).c_str());
+    } else if (v == "-g") {
+      const char* t = value("the minimum gamma");
+      if (!mic_abund_parse_text(t, 1, &f.gamma_num, &f.gamma_den)) usage_exit((std::string("The minimum gamma should be a decimal number in [0,1] (at most 9 decimals): ") + t).c_str());
+    } else if (v == "-a") {
+      const char* t = value("the minimum abundance");
+      if (!mic_abund_parse_text(t, 100, &a_num, &a_den)) usage_exit((std::string("The minimum abundance should be a decimal number in [0,100] (at most 9 decimals): ") + t).c_str());
+    } else if (v == "--highconfidence") {
+      f.conf_num = 75; f.conf_den = 100; f.gamma_num = 3; f.gamma_den = 100;
+    } else if (v == "--help" || v == "-h") {
+      usage_exit("");
+    } else {
+      usage_exit(("Failed to recognize option: " + v).c_str());
+    }
+  }
+  if (files.empty()) usage_exit("Please specify the result file(s) with -F.");
+
+  std::map<std::string, uint64_t> per_label;
+  uint64_t unassigned = 0, filtered = 0;
+  for (const std::string& path : files) {
+    std::ifstream in(path);
+    if (!in) { std::cerr << "Failed to open the result file: " << path << std::endl; return 1; }
+    std::string line;
+    size_t ln = 0;
+    while (std::getline(in, line)) {
+      ++ln;
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty()) continue;
+      if (ln == 1 && line.compare(0, 10, "Object_ID,") == 0) continue;      // header
+      // the last seven fields (the object name may hold commas)
+      std::string fld[7];
+      size_t end = line.size();
+      bool ok = true;
+      for (int j = 6; j >= 0; --j) {
+        const size_t c = line.rfind(',', end == 0 ? std::string::npos : end - 1);
+        if (c == std::string::npos || end == 0) { ok = false; break; }
+        fld[j] = line.substr(c + 1, end - c - 1);
+        end = c;
+      }
+      uint64_t s1 = 0, s2 = 0;
+      if (!ok || !parse_u32(fld[3], s1) || !parse_u32(fld[5], s2)) {
+        std::cerr << "Failed to read line " << ln << " of " << path << ": not a result line of CLARK's format." << std::endl;
+        return 1;
+      }
+      const std::string& first = fld[2];
+      if (first == "NA") { ++unassigned; continue; }
+      const bool conf = s1 * f.conf_den >= f.conf_num * (s1 + s2);
+      const bool gamma = decimal_at_least(fld[1], f.gamma_num, f.gamma_den);
+      if (conf && gamma) ++per_label[first];
+      else ++filtered;
+    }
+  }
+  std::vector<std::string> labels;
+  std::vector<uint64_t> counts = {unassigned, filtered};
+  for (const auto& kv : per_label) { labels.push_back(kv.first); counts.push_back(kv.second); }
+  mic::abund::Taxonomy tax;
+  if (!db.empty()) {
+    if (db.back() != '/') db.push_back('/');
+    mic::abund::load_taxonomy(db + "../taxonomy", tax);
+  }
+  const std::string table = mic::abund::format_table(counts, labels, &tax, a_num, a_den);
+  if (fwrite(table.data(), 1, table.size(), stdout) != table.size() || fflush(stdout) != 0) { std::cerr << "Failed to write the table." << std::endl; return 1; }
+  return 0;
+}

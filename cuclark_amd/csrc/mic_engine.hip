@@ -169,6 +169,7 @@ struct mic_engine {
   void* ingest = nullptr;      // device-side ingest state (mic_ingest.hip)
   uint64_t reserve_hbm = 0;         // mic_db_reserve_hbm: device memory the caller is allocating while the table builds
   uint32_t part = 0, n_parts = 0;   // mic_db_set_part: this engine answers for part `part` of `n_parts` of the database
+  MicAbund abund;                   // mic_abundance_*: the engine's counters (mic_abund.hip)
 };
 
 namespace {
@@ -605,6 +606,8 @@ int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int
 }
 
 void** mic_engine_ingest_slot(mic_engine* e) { return &e->ingest; }
+MicAbund* mic_engine_abund(mic_engine* e) { return &e->abund; }
+hipStream_t mic_engine_stream(mic_engine* e) { return e->stream; }
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down) { *up = e->up_stream; *down = e->down_stream; }
 
 void mic_build_report_add(const char* what, double seconds) {
@@ -704,6 +707,7 @@ int mic_destroy(mic_engine* e) {
   if (e->d_sizes) hipFree(e->d_sizes);
   if (e->d_flagged) hipFree(e->d_flagged);
   if (e->d_crowd) hipFree(e->d_crowd);
+  if (e->abund.d_counts) hipFree(e->abund.d_counts);
   if (e->ev0) mic_event_put(e->ev0);
   if (e->ev1) mic_event_put(e->ev1);
   if (e->stream) mic_stream_put(e->stream);

@@ -458,3 +458,22 @@ int mic_csv_line(char* buf, size_t cap, const uint8_t* name, size_t name_len, ui
 }
 
 }  // extern "C"
+
+// ---- abundance: the counting rule of mic_abund.h on the CPU (batches the host path classifies) ------------------------------
+#include "mic_abund.h"
+
+extern "C" {
+int mic_abundance_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets,
+                       const mic_abund_filter* filter, uint64_t* counts) {
+  if (!filter || !counts || (n_reads && !results)) return MIC_E_INVALID;
+  if (!mic_abund_filter_ok(*filter) || (!norm && filter->gamma_num) || n_targets > 65535) return MIC_E_INVALID;
+  for (size_t r = 0; r < n_reads; ++r)
+    ++counts[mic_abund_bucket(results + r * MIC_RESULT_WORDS, norm ? norm[r] : 0u, k, n_targets, *filter)];
+  return MIC_OK;
+}
+
+int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t* den) {
+  if (!num || !den) return MIC_E_INVALID;
+  return mic_abund_parse_text(text, max_int, num, den) ? MIC_OK : MIC_E_INVALID;
+}
+}  // extern "C"

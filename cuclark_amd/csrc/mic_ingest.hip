@@ -35,6 +35,7 @@ int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int
 int mic_set_error(int code, const char* fmt, ...);
 int mic_bind_thread_near_device(int device, int on);
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
+MicAbund* mic_engine_abund(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
 bool mic_peer_enable(int from, int to);
 
@@ -339,12 +340,34 @@ __global__ void __launch_bounds__(256) csv_fmt_kernel(CsvArgs a, const uint32_t*
   }
 }
 
+// (the caps are checked here as well as on the host: the counting kernel behind this one reads the status word on the device)
 __global__ void csv_finish_kernel(const uint32_t* __restrict__ line_off, uint32_t n_reads, const uint32_t* __restrict__ flagged,
-                                  const uint32_t* __restrict__ rp, uint32_t* __restrict__ hdr) {
+                                  const uint32_t* __restrict__ rp, uint32_t csv_cap, uint32_t cont_cap, uint32_t* __restrict__ hdr) {
   hdr[H_CSV_BYTES] = line_off[n_reads];
   hdr[H_FLAGGED] = flagged[0];
   hdr[H_CONT] = rp[n_reads];
   if (flagged[0]) atomicOr(&hdr[H_STATUS], (uint32_t)MIC_INGEST_DENSE);
+  if (line_off[n_reads] > csv_cap || rp[n_reads] > cont_cap) atomicOr(&hdr[H_STATUS], (uint32_t)MIC_INGEST_TOO_MANY);
+}
+
+// MIC_INGEST_NO_CSV: what csv_len_kernel + csv_finish_kernel report that does not come from the lengths of the CSV lines - a gamma the
+// formatter does not cover (csv_len_kernel: mic_fmt_gamma < 0), a read that needs the dense path, more containers than the slot holds
+__global__ void __launch_bounds__(256) nocsv_status_kernel(const uint32_t* __restrict__ results, const uint32_t* __restrict__ length, int paired, int k,
+                                                           uint32_t n_reads, const uint32_t* __restrict__ flagged, const uint32_t* __restrict__ rp,
+                                                           uint32_t cont_cap, uint32_t* __restrict__ hdr) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r < n_reads) {
+    const uint32_t total = results[(size_t)r * 8], norm = paired ? length[r] - 1u : length[r];
+    const double den = ((double)norm - (double)k) + 1.0;
+    if (total != 0 && !(den >= (double)total)) atomicOr(&hdr[H_STATUS], (uint32_t)MIC_INGEST_ODD_RECORD);
+  }
+  if (r == 0) {
+    hdr[H_CSV_BYTES] = 0;
+    hdr[H_FLAGGED] = flagged[0];
+    hdr[H_CONT] = rp[n_reads];
+    if (flagged[0]) atomicOr(&hdr[H_STATUS], (uint32_t)MIC_INGEST_DENSE);
+    if (rp[n_reads] > cont_cap) atomicOr(&hdr[H_STATUS], (uint32_t)MIC_INGEST_TOO_MANY);
+  }
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -982,6 +1005,7 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   for (size_t p = 0; p < n_group; ++p) if (!group[p]) return mic_set_error(MIC_E_INVALID, "null engine in the group");
   mic_engine* e = group[owner];
   const int paired = flags & MIC_INGEST_PAIRED;
+  const bool no_csv = (flags & MIC_INGEST_NO_CSV) != 0;
   const uint32_t lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;      // lines per FASTQ record
   if (!e || !out) return mic_set_error(MIC_E_INVALID, "null argument");
   Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
@@ -1062,10 +1086,22 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   CsvArgs ca;
   ca.raw = s.d_raw; ca.name_s = s.rec.name_s; ca.name_len = s.rec.name_len; ca.length = s.rec.length; ca.results = s.d_results;
   ca.tnames = g->d_tnames; ca.tname_off = g->d_tname_off; ca.n_targets = g->n_targets; ca.n_reads = n_reads; ca.k = k; ca.paired = paired ? 1 : 0;
-  csv_len_kernel<<<gr, 256, 0, st>>>(ca, s.d_line_len, s.d_hdr);
-  tb = s.tmp_bytes;
-  ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_line_len, s.d_line_off, (int)(n_reads + 1), st));
-  csv_finish_kernel<<<1, 1, 0, st>>>(s.d_line_off, n_reads, s.d_flagged, s.d_rp, s.d_hdr);
+  const uint32_t cont_cap = (uint32_t)std::min<size_t>(g->cont_cap, 0xFFFFFFFFu);
+  if (!no_csv) {
+    csv_len_kernel<<<gr, 256, 0, st>>>(ca, s.d_line_len, s.d_hdr);
+    tb = s.tmp_bytes;
+    ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_line_len, s.d_line_off, (int)(n_reads + 1), st));
+    csv_finish_kernel<<<1, 1, 0, st>>>(s.d_line_off, n_reads, s.d_flagged, s.d_rp, (uint32_t)std::min<size_t>(g->csv_cap, 0xFFFFFFFFu), cont_cap, s.d_hdr);
+  } else {
+    nocsv_status_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(s.d_results, s.rec.length, paired ? 1 : 0, k, n_reads, s.d_flagged, s.d_rp, cont_cap, s.d_hdr);
+  }
+  {  // abundance counters of the slot's engine (the owner of a table-sharded batch): the kernel adds nothing when the status word says
+     // the batch goes back to the host path
+    MicAbund& ab = *mic_engine_abund(e);
+    if (ab.on && ab.d_counts && ab.n_words == nt + 2)
+      ITRY(mic_launch_abund(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ab, ab.d_counts, s.d_hdr + H_STATUS, st));
+  }
+  if (no_csv && g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, st));
   ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));
   ITRY(hipEventRecord(s.ev, st));
   ITRY(wait_event(s.ev));
@@ -1076,6 +1112,13 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   uint32_t status = s.h_hdr[H_STATUS];
   if (csv_bytes > g->csv_cap || s.h_hdr[H_CONT] > g->cont_cap) status |= MIC_INGEST_TOO_MANY;
   if (status) { out->status = MIC_INGEST_FALLBACK | status; return MIC_OK; }
+  if (no_csv) {
+    out->n_reads = n_reads; out->csv_bytes = 0; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
+    out->status = MIC_INGEST_OK;
+    if (timing) fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+count %.0f us, no csv\n", slot_id, nb, n_reads,
+                        (t1 - t0) * 1e6, (t2 - t1) * 1e6);
+    return MIC_OK;
+  }
   // ---- phase 3: CSV text -> host
   csv_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ca, s.d_line_off, s.d_csv);
   ITRY(hipGetLastError());

@@ -214,4 +214,17 @@ void mic_stream_put(hipStream_t s);                        // drained first; nul
 hipError_t mic_event_get(hipEvent_t* ev, bool timing);     // an event of the current device
 void mic_event_put(hipEvent_t ev);
 
+// ---- abundance counters (mic_abund.hip) ----------------------------------------------------------------------------------------
+// An engine's counters while mic_abundance_start is in force: n_words = num_targets + 2 u64 on the engine's device.
+struct MicAbund {
+  unsigned long long* d_counts = nullptr;
+  uint32_t n_words = 0;
+  bool on = false;
+  uint64_t conf_num = 5, conf_den = 10, gamma_num = 0, gamma_den = 1;
+};
+// adds reads [0, n) of `results` to `counts` by the rule of mic_abund.h: norm of read r = norm[r] - norm_sub (norm == nullptr: 0);
+// status != nullptr: a non-zero *status (the batch is handed back) makes the launch add nothing
+hipError_t mic_launch_abund(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
+                            const MicAbund& f, unsigned long long* counts, const uint32_t* status, hipStream_t s);
+
 #endif

@@ -310,12 +310,14 @@ class MiClarkDB:
         self._ingest = dict(raw=[_as_np(raw[i], (max_bytes,), np.uint8) for i in range(n_slots)], max_bytes=max_bytes)
         return self._ingest["raw"]
 
-    def ingest_classify(self, slot, data, paired=False):
-        """data: bytes of whole records.  Returns dict(status, n_reads, csv (bytes), results (u32[n,8] or None))."""
+    def ingest_classify(self, slot, data, paired=False, csv=True):
+        """data: bytes of whole records.  Returns dict(status, n_reads, csv (bytes), results (u32[n,8] or None)).
+        csv=False: MIC_INGEST_NO_CSV (no CSV text, csv is b"")."""
         buf = np.frombuffer(data, np.uint8)
         self._ingest["raw"][slot][: buf.size] = buf
         out = _lib.MicIngestResult()
-        check(self.L.mic_ingest_classify(self.h, slot, buf.size, int(bool(paired)), C.byref(out)))
+        flags = int(bool(paired)) | (0 if csv else _lib.MIC_INGEST_NO_CSV)
+        check(self.L.mic_ingest_classify(self.h, slot, buf.size, flags, C.byref(out)))
         r = dict(status=int(out.status), n_reads=int(out.n_reads), n_lines=int(out.n_lines), csv=None, results=None)
         if out.status == 0:
             r["csv"] = C.string_at(out.csv, out.csv_bytes) if out.csv_bytes else b""
@@ -324,20 +326,43 @@ class MiClarkDB:
         return r
 
     @staticmethod
-    def ingest_classify_group(group, owner, slot, data, paired=False):
+    def ingest_classify_group(group, owner, slot, data, paired=False, csv=True):
         """Table-sharded ingest (mic_ingest_classify_group): group[p] holds part p of len(group) parts, the slot belongs to group[owner]."""
         e = group[owner]
         buf = np.frombuffer(data, np.uint8)
         e._ingest["raw"][slot][: buf.size] = buf
         out = _lib.MicIngestResult()
         hs = (C.c_void_p * len(group))(*[g.h for g in group])
-        check(e.L.mic_ingest_classify_group(hs, len(group), owner, slot, buf.size, int(bool(paired)), C.byref(out)))
+        flags = int(bool(paired)) | (0 if csv else _lib.MIC_INGEST_NO_CSV)
+        check(e.L.mic_ingest_classify_group(hs, len(group), owner, slot, buf.size, flags, C.byref(out)))
         r = dict(status=int(out.status), n_reads=int(out.n_reads), n_lines=int(out.n_lines), csv=None, results=None)
         if out.status == 0:
             r["csv"] = C.string_at(out.csv, out.csv_bytes) if out.csv_bytes else b""
             if out.results:
                 r["results"] = _as_np(out.results, (int(out.n_reads), MIC_RESULT_WORDS), np.uint32).copy()
         return r
+
+    # -- abundance profile (mic_abundance_*): filt is a _lib.MicAbundFilter (host.abund_filter)
+    def abundance_start(self, filt=None):
+        """Zero and enable the engine's device counters: every ingest batch that returns MIC_INGEST_OK adds its reads."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_abundance_start(self.h, C.byref(f)))
+
+    def abundance_fetch(self):
+        """u64[num_targets + 2]: [0] unassigned, [1] filtered out, [t + 2] target t (waits for the device)."""
+        out = np.zeros(self.num_targets + 2, np.uint64)
+        check(self.L.mic_abundance_fetch(self.h, out.ctypes.data, out.size))
+        return out
+
+    def abundance_stop(self):
+        check(self.L.mic_abundance_stop(self.h))
+
+    def abundance_device(self, d_results, d_norm, n_reads, d_counts, filt=None, stream=0):
+        """The rule on caller-owned device memory (e.g. torch tensors' data_ptr()): counts ADDED to d_counts (u64[num_targets + 2])."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_abundance_device(self.h, d_results, d_norm or None, n_reads, C.byref(f), d_counts, stream or None))
 
     def ingest_fetch_group_rows(self, slot, part):
         """test hook: the partial rows engine `part` of the group computed for the slot's last table-sharded batch"""

@@ -89,3 +89,34 @@ def build_db(target_files, target_labels, k, htsize, out_prefix, key_bytes=0, mi
     if rc != 0:
         raise RuntimeError(f"mic_db_build failed ({rc}): {L.mic_db_build_error().decode(errors='replace')}")
     return int(n.value)
+
+
+def parse_threshold(text, max_int=1):
+    """A threshold as the command lines take it (mic_abund_parse): (num, den) with den = 10^d, d <= 9; ValueError otherwise."""
+    num, den = C.c_uint64(0), C.c_uint64(0)
+    if _lib.load().mic_abund_parse(text.encode() if isinstance(text, str) else text, int(max_int), C.byref(num), C.byref(den)) != 0:
+        raise ValueError(f"not a threshold in [0, {max_int}] with at most 9 decimals: {text!r}")
+    return int(num.value), int(den.value)
+
+
+def abund_filter(confidence="0.5", gamma="0"):
+    """mic_abund_filter from decimal strings (CLARK's defaults: -c 0.5 -g 0)."""
+    cn, cd = parse_threshold(confidence)
+    gn, gd = parse_threshold(gamma)
+    return _lib.MicAbundFilter(cn, cd, gn, gd)
+
+
+def abundance_host(results, norm, k, n_targets, filt=None):
+    """mic_abundance_host: u64[n_targets + 2] counts of the result rows (u32[n, 8]) by the rule of csrc/mic_abund.h
+    ([0] unassigned, [1] filtered out, [t + 2] target t).  norm: the CSV's Length column per read, or None (no gamma filter)."""
+    L = _lib.load()
+    results = np.ascontiguousarray(results, np.uint32).reshape(-1, 8)
+    n = results.shape[0]
+    nm = np.ascontiguousarray(norm, np.uint32) if norm is not None else None
+    counts = np.zeros(int(n_targets) + 2, np.uint64)
+    f = filt if filt is not None else abund_filter()
+    rc = L.mic_abundance_host(results.ctypes.data, nm.ctypes.data if nm is not None else None, n, int(k), int(n_targets), C.byref(f),
+                              counts.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_abundance_host: invalid argument ({rc})")
+    return counts

@@ -285,6 +285,9 @@ int mic_debug_fetch_crowd(mic_engine* e, uint32_t* out, size_t words, uint32_t c
                                       (mic_pairs_merge_to_slot, with MIC_INGEST_PAIRED) or records of a FASTA text
                                       (mic_text_to_slot): nothing is uploaded                                                    */
 #define MIC_INGEST_RESIDENT_FASTQ 12 /* flags: as MIC_INGEST_RESIDENT, and the text is four-line FASTQ (mic_text_to_slot), not merged pairs */
+#define MIC_INGEST_NO_CSV 16       /* flags: no CSV (summary-only runs: mic_abundance_*): the CSV kernels and the copy of the text are
+                                      skipped, csv_bytes is 0; results still come back with want_results, the status bits that
+                                      do not come from CSV line lengths are raised as without the flag                          */
 #define MIC_INGEST_OK 0u
 #define MIC_INGEST_FALLBACK 1u     /* run the host path on this batch                                        */
 #define MIC_INGEST_ODD_RECORD 2u   /* empty read name, FASTA record without a sequence line, unknown format   */
@@ -420,6 +423,37 @@ int mic_text_offsets(const mic_text* p, const uint64_t** samples, size_t* n_samp
 int mic_text_to_slot(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, size_t slot, size_t* n_bytes);
 int mic_text_copy(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, void* host_dst, size_t cap, size_t* n_bytes);
 int mic_text_free(mic_engine* e, mic_text* p);
+
+/* ---- abundance profile: reads per target, counted on the device (CLARK's estimate_abundance step) ----------------------
+ * A read's result row goes into one of num_targets + 2 u64 counters (csrc/mic_abund.h: the rule, shared by host and device):
+ *   [0] unassigned (idxBest == 0), [1] assigned but filtered out, [idxBest + 1] the read counts for target idxBest - 1.
+ * The filter: confidence best / (best + second) >= conf_num / conf_den and gamma sum / (norm - k + 1) >= gamma_num / gamma_den
+ * (gamma_num == 0: no gamma filter), exact integer arithmetic; denominators are 10^d, d <= 9, numerators <= denominators.
+ * norm = the CSV's Length column (the read's length, minus 1 for a merged pair).
+ * mic_abundance_start   zeroes and enables the engine's counters: from then on every ingest batch of this engine that returns
+ *                       MIC_INGEST_OK (mic_ingest_classify, or mic_ingest_classify_group with this engine as the owner) adds its
+ *                       reads on the device; a batch handed back (MIC_INGEST_FALLBACK) adds nothing - the caller counts it
+ *                       (mic_abundance_host) where it classifies it.  The batch API (mic_batch_*) does not count.
+ * mic_abundance_fetch   waits for the engine's device, then copies the counters (n = num_targets + 2 words) out.
+ * mic_abundance_stop    disables counting (the counters keep their values).
+ * mic_abundance_device  the same rule on caller-owned device memory: d_results (MIC_RESULT_WORDS u32 per read), d_norm (u32 per
+ *                       read; NULL: only a filter without gamma), counts ADDED to d_counts (num_targets + 2 u64).  Asynchronous
+ *                       on `stream` (NULL = the engine's stream).
+ * mic_abundance_host    the rule on the CPU (no device needed): counts added to counts[n_targets + 2].
+ * mic_abund_parse       a threshold as the command lines take it ("0.75": digits, one optional '.', at most 9 fractional digits,
+ *                       value in [0, max_int]; no sign, exponent or blanks) into num / den; MIC_E_INVALID otherwise. */
+typedef struct mic_abund_filter {
+  uint64_t conf_num, conf_den;    /* minimum confidence conf_num / conf_den (CLARK's default 0.5 = 5 / 10)       */
+  uint64_t gamma_num, gamma_den;  /* minimum gamma (CLARK's default 0 = 0 / 1: no gamma filter)                   */
+} mic_abund_filter;
+int mic_abundance_start(mic_engine* e, const mic_abund_filter* filter);
+int mic_abundance_fetch(mic_engine* e, uint64_t* counts, size_t n);
+int mic_abundance_stop(mic_engine* e);
+int mic_abundance_device(mic_engine* e, const uint32_t* d_results, const uint32_t* d_norm, size_t n_reads, const mic_abund_filter* filter,
+                         uint64_t* d_counts, void* stream);
+int mic_abundance_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets,
+                       const mic_abund_filter* filter, uint64_t* counts);
+int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t* den);
 
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */

@@ -195,6 +195,10 @@ int mic_gz_copy_text(mic_engine*, const void* t, size_t off, size_t n, void* dst
 int mic_gz_reserve(mic_engine*, size_t, uint32_t) { return MIC_OK; }
 uint64_t mic_gz_reserve_bytes(size_t, uint32_t) { return 0; }
 int mic_gz_release(mic_engine*) { return MIC_OK; }
+// abundance counters: the mock classifies nothing into buckets, its counters stay zero
+int mic_abundance_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
+int mic_abundance_fetch(mic_engine*, uint64_t* counts, size_t n) { for (size_t i = 0; i < n; ++i) counts[i] = 0; return MIC_OK; }
+int mic_abundance_stop(mic_engine*) { return MIC_OK; }
 }  // extern "C"
 
 namespace {
