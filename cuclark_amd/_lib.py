@@ -17,6 +17,8 @@ MIC_RESULT_WORDS = 8
 MIC_FLAG_ROW_OVERFLOW = 1
 MIC_FLAG_DENSE_PATH = 2
 MIC_ROW_INVALID = 0xFFFFFFFF
+MIC_ROLLUP_WORDS, MIC_ROLLUP_MAX_LEVELS = 8, 7
+MIC_ROLLUP_UNRESOLVED, MIC_ROLLUP_PENDING = 0xFFFFFFFF, 0xFFFFFFFE
 MIC_LAYOUT_AUTO, MIC_LAYOUT_DIRECT, MIC_LAYOUT_MINIMIZER, MIC_LAYOUT_SUPER, MIC_LAYOUT_SUPER2 = 0, 1, 2, 3, 4
 
 
@@ -136,6 +138,17 @@ SYMBOLS = [
     ("mic_abundance_device", C.c_int, [_VP, _VP, _VP, _SZ, C.POINTER(MicAbundFilter), _VP, _VP]),
     ("mic_abundance_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, C.POINTER(MicAbundFilter), _VP]),
     ("mic_abund_parse", C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("mic_rollup_check", C.c_int, [C.c_uint32, C.c_uint32, _VP]),
+    ("mic_rollup_set", C.c_int, [_VP, C.c_uint32, _VP]),
+    ("mic_rollup_layout", C.c_int, [_VP, _VP, C.POINTER(C.c_uint64)]),
+    ("mic_rollup_device", C.c_int, [_VP, _VP, _VP, _SZ, C.POINTER(MicAbundFilter), _VP, _VP, _VP, _VP]),
+    ("mic_rollup_dense_device", C.c_int, [_VP, _VP, _VP, _SZ, _VP, C.POINTER(MicAbundFilter), _VP, _VP, _VP, _VP]),
+    ("mic_rollup_host", C.c_int, [_VP, C.c_uint32, _VP, _VP, _SZ, C.c_int, C.c_uint32, C.c_uint32, _VP, C.POINTER(MicAbundFilter),
+                                  _VP, _VP, _VP]),
+    ("mic_rollup_start", C.c_int, [_VP, C.POINTER(MicAbundFilter)]),
+    ("mic_rollup_fetch", C.c_int, [_VP, _VP, _SZ]),
+    ("mic_rollup_stop", C.c_int, [_VP]),
+    ("mic_ingest_rollup_rows", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     ("mic_format_ratio_g", C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p]),
     ("mic_key_bytes_rule", C.c_int, [C.c_uint64, C.c_int]),
     ("mic_index_reads", C.c_long, [_VP, _SZ, _SZ, _U64P, _U64P, _U64P, _U64P, _U64P]),

@@ -174,6 +174,18 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     }
   }
   groups_ = use / parts_;
+  if (ranking()) {   // the lineage first: a run that cannot be rolled up ends before the database is loaded
+    std::string err;
+    bool ok;
+    if (!opt_.lineage.empty()) ok = rank::lineage_from_file(opt_.lineage, names_, lineage_, err);
+    else {
+      abund::Taxonomy tax;
+      if (!rank::load_taxonomy(opt_.folder + "../taxonomy", tax))
+        die("--rank-report needs a lineage: no taxonomy (nodes.dmp) in " + opt_.folder + "../taxonomy and no --lineage <tsv>.");
+      ok = rank::lineage_from_taxonomy(names_, tax, lineage_, err);
+    }
+    if (!ok) die(err);
+  }
   std::cerr << "Loading database [" << db << ".*] (s=" << opt_.sampling << ")..." << std::endl;
   const size_t per_engine_batches = std::max<size_t>(1, (opt_.batches + groups_ - 1) / groups_);
   for (size_t d = 0; d < use; ++d) {
@@ -181,7 +193,7 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     memset(&cfg, 0, sizeof(cfg));
     cfg.device = (int)(d % (size_t)n_dev); cfg.k = (int)opt_.k; cfg.num_targets = (uint32_t)(names_.size());
     cfg.num_batches = (uint32_t)per_engine_batches;
-    cfg.row_words = opt_.extended ? (uint32_t)std::min<size_t>(names_.size() + 1, 65) : 16;
+    cfg.row_words = (opt_.extended || ranking()) ? (uint32_t)std::min<size_t>(names_.size() + 1, 65) : 16;   // (roll-up reads the rows)
     mic_engine* e = nullptr;
     check(mic_create(&cfg, &e), "engine creation");
     engines_.push_back(e);
@@ -218,6 +230,7 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
   if (slots.joinable()) slots.join();
   for (mic_engine* e : engines_) mic_db_reserve_hbm(e, 0);
   if (!load_err.empty()) die(load_err);
+  if (ranking()) for (mic_engine* e : engines_) check(mic_rollup_set(e, lineage_.n_levels, lineage_.group_of.data()), "lineage");
   {  // a default layout that was given up for another one is said, with the reason (the rate depends on it: DESIGN.md 5.3)
     std::istringstream rep(mic_db_last_build_report());
     std::string ln;
@@ -237,6 +250,11 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
 }
 
 void Classifier::reset_counts() {
+  if (ranking()) {
+    for (mic_engine* e : engines_) check(mic_rollup_start(e, &opt_.abund_filter), "roll-up counters");
+    std::lock_guard<std::mutex> lk(count_mu_);
+    host_rollup_.assign(lineage_.n_counters(), 0);
+  }
   if (!counting()) return;
   for (mic_engine* e : engines_) check(mic_abundance_start(e, &opt_.abund_filter), "abundance counters");
   std::lock_guard<std::mutex> lk(count_mu_);
@@ -261,6 +279,17 @@ std::vector<uint64_t> Classifier::abundance_counts() {
   }
   std::lock_guard<std::mutex> lk(count_mu_);
   for (size_t i = 0; i < host_counts_.size() && i < total.size(); ++i) total[i] += host_counts_[i];
+  return total;
+}
+
+std::vector<uint64_t> Classifier::rollup_counts() {
+  std::vector<uint64_t> total(lineage_.n_counters(), 0), part(lineage_.n_counters());
+  for (mic_engine* e : engines_) {
+    check(mic_rollup_fetch(e, part.data(), part.size()), "roll-up counters");
+    for (size_t i = 0; i < part.size(); ++i) total[i] += part[i];
+  }
+  std::lock_guard<std::mutex> lk(count_mu_);
+  for (size_t i = 0; i < host_rollup_.size() && i < total.size(); ++i) total[i] += host_rollup_[i];
   return total;
 }
 
@@ -407,6 +436,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
   }
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
+  if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   std::ifstream o_fd(objects), r_fd(results);
   std::string o_line, r_line;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;
@@ -486,6 +516,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
   }
   if (!list_mode) { one(f1, f2, results, false); return; }
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
+  if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   std::ifstream o1(f1), o2(f2), r_fd(results);
   std::string a, b, r;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;

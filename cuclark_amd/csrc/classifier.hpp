@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mi_clark.h"
+#include "rank_report.hpp"
 
 namespace mic {
 
@@ -34,6 +35,7 @@ struct Options {
   std::string targets, folder, objects, objects2, results;   // results empty: no result CSV (a summary-only --abundance run)
   std::string abundance;                                     // --abundance <file>: the abundance profile is counted (mic_abundance_*)
   mic_abund_filter abund_filter = {5, 10, 0, 1};             // --min-confidence / --min-gamma / --highconfidence (CLARK's -c 0.5 -g 0)
+  std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
 };
 
 class Classifier {
@@ -85,6 +87,10 @@ class Classifier {
   // --abundance: reads per bucket of the run (include/mi_clark.h: [0] unassigned, [1] filtered out, [t + 2] target t), the device
   // counters of all engines plus what the host path counted
   std::vector<uint64_t> abundance_counts();
+  // --rank-report: the roll-up counters of the run (include/mi_clark.h: [0] no hit, [1] unresolved, [2 + off_l + g]), summed the same
+  // way, and the lineage they were counted along (from --lineage, else from <database directory>/../taxonomy)
+  std::vector<uint64_t> rollup_counts();
+  const rank::Lineage& lineage() const { return lineage_; }
 
   std::string db_name() const;  // getdbName, CuCLARK_hh.hh:580-591
   const std::vector<std::string>& target_names() const { return names_; }
@@ -116,6 +122,9 @@ class Classifier {
   std::atomic<size_t> n_objects_{0};
   // --abundance: every run over the input starts the counters afresh (a run the feeder gives up is repeated from the start)
   bool counting() const { return !opt_.abundance.empty(); }
+  bool ranking() const { return !opt_.rank_report.empty(); }
+  rank::Lineage lineage_;
+  std::vector<uint64_t> host_rollup_;
   void reset_counts();
   void count_host(const std::vector<uint32_t>& results, const std::vector<uint32_t>& norm);
   std::vector<uint64_t> host_counts_;

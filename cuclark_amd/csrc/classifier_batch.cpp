@@ -21,7 +21,7 @@ void Classifier::ensure_batches(size_t max_reads, size_t max_cont) {
   slots_per_engine_ = std::max<size_t>(1, (opt_.batches + groups_ - 1) / groups_);
   slot_reads_ = max_reads + max_reads / 8 + 64;
   slot_cont_ = max_cont + max_cont / 8 + 64;
-  row_words_ = opt_.extended ? (uint32_t)std::min<size_t>(names_.size() + 1, 65) : 16;
+  row_words_ = (opt_.extended || ranking()) ? (uint32_t)std::min<size_t>(names_.size() + 1, 65) : 16;
   lent_.resize(n_eng);
   std::vector<uint32_t> index(slots_per_engine_ + 1);
   for (size_t i = 0; i <= slots_per_engine_; ++i) index[i] = (uint32_t)(i * slot_reads_);   // fixed stride: slot i owns rows [i*S, (i+1)*S)
@@ -29,7 +29,7 @@ void Classifier::ensure_batches(size_t max_reads, size_t max_cont) {
     Lent& L = lent_[d];
     L.rp.resize(slots_per_engine_); L.ct.resize(slots_per_engine_);
     check(mic_batches_alloc(engines_[d], slots_per_engine_ * slot_reads_, slot_reads_, slot_cont_, index.data(),
-                            (opt_.extended || parts_ > 1) ? 1 : 0,
+                            (opt_.extended || parts_ > 1 || ranking()) ? 1 : 0,
                             &L.results, &L.rows, L.rp.data(), L.ct.data()), "batch allocation");
   }
 }
@@ -169,7 +169,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       tick(t_pack);
       if (!sharded) {
         check(mic_batch_ready(engines_[d], lb, cnt, m), "readyBatch");
-        check(mic_batch_query(engines_[d], lb, opt_.extended ? 1 : 0, 0), "queryBatch");
+        check(mic_batch_query(engines_[d], lb, (opt_.extended || ranking()) ? 1 : 0, 0), "queryBatch");
         check(mic_batch_wait(engines_[d], lb), "waitForBatch");
       } else {
         // every engine of the group probes the same reads against its part of the table - one upload into the first engine, the packed
@@ -186,7 +186,10 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       std::vector<char> line(line_cap);
       std::vector<uint32_t> dense;
       std::vector<uint32_t> ab_res, ab_norm;        // --abundance: the batch's result rows as the CSV shows them, and the Length column
-      if (counting()) { ab_res.resize(cnt * MIC_RESULT_WORDS); ab_norm.resize(cnt); }
+      if (counting()) ab_res.resize(cnt * MIC_RESULT_WORDS);
+      if (counting() || ranking()) ab_norm.resize(cnt);
+      // --rank-report: this batch's roll-up counters, from its sparse rows and - a read at a time - the dense counts of the rows that did not fit
+      std::vector<uint64_t> ru_counts(ranking() ? lineage_.n_counters() : 0, 0);
       const uint32_t* res = L.results + lb * slot_reads_ * MIC_RESULT_WORDS;
       const uint32_t* rows = L.rows ? L.rows + lb * slot_reads_ * row_words : nullptr;
       for (size_t i = 0; i < cnt; ++i) {
@@ -221,10 +224,11 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
           }
           dn = dense.data();
         }
-        if (counting()) {
-          memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
-          ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
-        }
+        if (counting()) memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
+        if (counting() || ranking()) ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
+        if (ranking() && dn)
+          check(mic_rollup_host(nullptr, 0, dn, &ab_norm[i], 1, k, T, lineage_.n_levels, lineage_.group_of.data(), &opt_.abund_filter, nullptr, nullptr,
+                                ru_counts.data()), "roll-up (host path, dense counts)");
         if (!emit) continue;
         int w = mic_csv_line(line.data(), line.size(), map + name_s[r], (size_t)(name_e[r] - name_s[r]), length[r], paired ? 1 : 0,
                              k, rr, nm.data(), T, opt_.extended ? 1 : 0, row, dn);
@@ -232,6 +236,13 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
         s.append(line.data(), (size_t)w);
       }
       if (counting()) count_host(ab_res, ab_norm);
+      if (ranking()) {
+        check(mic_rollup_host(rows, row_words, nullptr, ab_norm.data(), cnt, k, T, lineage_.n_levels, lineage_.group_of.data(), &opt_.abund_filter,
+                              nullptr, nullptr, ru_counts.data()), "roll-up (host path)");
+        std::lock_guard<std::mutex> lk(count_mu_);
+        if (host_rollup_.size() != ru_counts.size()) host_rollup_.assign(ru_counts.size(), 0);
+        for (size_t j = 0; j < ru_counts.size(); ++j) host_rollup_[j] += ru_counts[j];
+      }
     } catch (const std::exception& ex) {
       std::lock_guard<std::mutex> lk(wmu);
       if (err.empty()) err = ex.what();

@@ -54,6 +54,9 @@ static void print_usage(const char* prog) {
                "                     default: the smallest number of parts that fit a GPU's memory\n";
   std::cout << "--abundance <file>,  also count the abundance profile of the objects (CLARK's estimate_abundance table) into <file>;\n"
                "                     without -R no result CSV is written (summary-only run)\n";
+  std::cout << "--rank-report <file> [--lineage <tsv>],  also resolve every object at the lowest rank whose confidence passes --min-confidence\n"
+               "                     and count the objects per rank and group into <file>; the lineage of the targets comes from <tsv>\n"
+               "                     (label<TAB>name_1<TAB>...<TAB>name_L per target) or from <DB>/../taxonomy; works without -R like --abundance\n";
   std::cout << "--min-confidence <c>, --min-gamma <g>, --highconfidence (= --min-confidence 0.75 --min-gamma 0.03), --min-abundance <a>:\n"
                "                     the filters of the abundance profile (CLARK's -c, -g, --highconfidence, -a; defaults 0.5, 0, 0)\n";
   std::cout << "--tsk, --extended, --light, --htsize <n>, --help, --version\n\n";
@@ -144,7 +147,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance;
+  std::string abundance, rank_report, lineage;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
 
@@ -183,6 +186,13 @@ int main(int argc, char** argv) {
     }
     if (val == "--light") { light = true; continue; }
     if (val == "--abundance") { need("Please specify the file of the abundance profile!"); abundance = argv[i]; continue; }
+    if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
+    if (val == "--lineage") {
+      need("Please specify the lineage file!");
+      lineage = argv[i];
+      if (!valid_file(argv[i])) { std::cerr << "Failed to find/read the lineage file: " << argv[i] << std::endl; exit(1); }
+      continue;
+    }
     if (val == "--min-confidence" || val == "--min-gamma" || val == "--min-abundance") {
       need("Please specify the threshold!");
       const bool a = val == "--min-abundance";
@@ -265,11 +275,12 @@ int main(int argc, char** argv) {
   } else {
     gap = 0;
   }
-  if (!abundance.empty() && i_results < 0 && ext) {
+  if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
+  if ((!abundance.empty() || !rank_report.empty()) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty())) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty())) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -287,6 +298,7 @@ int main(int argc, char** argv) {
   o.results = i_results >= 0 ? argv[i_results] : "";
   o.abundance = abundance;
   o.abund_filter = ab_filter;
+  o.rank_report = rank_report; o.lineage = lineage;
   mic::Classifier* classifier = nullptr;
   try {
     classifier = new mic::Classifier(o);
@@ -300,6 +312,13 @@ int main(int argc, char** argv) {
       if (!f || fwrite(table.data(), 1, table.size(), f) != table.size() || fclose(f) != 0)
         throw std::runtime_error("Failed to write the abundance profile: " + abundance);
       std::cout << " - Abundance profile stored in " << abundance << std::endl;
+    }
+    if (!rank_report.empty()) {
+      const std::string report = mic::rank::format_report(classifier->rollup_counts(), classifier->lineage());
+      FILE* f = fopen(rank_report.c_str(), "wb");
+      if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the rank report: " + rank_report);
+      std::cout << " - Rank report stored in " << rank_report << std::endl;
     }
   } catch (const std::exception& ex) {
     std::cerr << ex.what() << std::endl;

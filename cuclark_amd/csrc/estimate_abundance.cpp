@@ -5,10 +5,15 @@
 // mic_abund.h: the confidence is decided exactly from score1 and score2, the gamma from the printed Gamma text, compared as a
 // decimal.  The table (abundance_table.hpp) goes to stdout; names and lineages come from <-D>/../taxonomy, the layout set_targets.sh
 // makes, as for exe/cuCLARK --abundance.
+//   estimate_abundance -F <extended.csv> ... --rank-report <file> [--lineage <tsv> | -D <database directory>]
+// also writes the rank roll-up report (rank_report.hpp; the rule: mic_rollup.h) into <file>: every read's per-target counts - an
+// --extended result CSV carries them, a plain one is refused - are summed along the lineage and the read is counted at the lowest
+// level whose confidence passes -c (gamma as above).  The lineage comes from --lineage, else from <-D>/../taxonomy.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -17,13 +22,16 @@
 
 #include "abundance_table.hpp"
 #include "mic_abund.h"
+#include "mic_rollup.h"
+#include "rank_report.hpp"
 
 namespace {
 
 [[noreturn]] void usage_exit(const char* msg) {
   if (msg && *msg) std::cerr << msg << std::endl;
   std::cerr << "Usage: estimate_abundance -F <result.csv> [<result.csv> ...] [-D <database directory>] [-c <min confidence in [0,1]>]"
-               " [-g <min gamma in [0,1]>] [-a <min abundance in [0,100]>] [--highconfidence]" << std::endl;
+               " [-g <min gamma in [0,1]>] [-a <min abundance in [0,100]>] [--highconfidence]"
+               " [--rank-report <file> [--lineage <tsv>]]" << std::endl;
   exit(1);
 }
 
@@ -78,7 +86,7 @@ bool parse_u32(const std::string& s, uint64_t& v) {
 
 int main(int argc, char** argv) {
   std::vector<std::string> files;
-  std::string db;
+  std::string db, rank_report, lineage_file;
   mic_abund_filter f = {5, 10, 0, 1};
   uint64_t a_num = 0, a_den = 1;
   for (int i = 1; i < argc; ++i) {
@@ -101,6 +109,10 @@ int main(int argc, char** argv) {
     } else if (v == "-a") {
       const char* t = value("the minimum abundance");
       if (!mic_abund_parse_text(t, 100, &a_num, &a_den)) usage_exit((std::string("The minimum abundance should be a decimal number in [0,100] (at most 9 decimals): ") + t).c_str());
+    } else if (v == "--rank-report") {
+      rank_report = value("the file of the rank report");
+    } else if (v == "--lineage") {
+      lineage_file = value("the lineage file");
     } else if (v == "--highconfidence") {
       f.conf_num = 75; f.conf_den = 100; f.gamma_num = 3; f.gamma_den = 100;
     } else if (v == "--help" || v == "-h") {
@@ -110,6 +122,16 @@ int main(int argc, char** argv) {
     }
   }
   if (files.empty()) usage_exit("Please specify the result file(s) with -F.");
+  if (rank_report.empty() && !lineage_file.empty()) usage_exit("--lineage goes with --rank-report <file>.");
+  if (!rank_report.empty() && lineage_file.empty() && db.empty()) usage_exit("--rank-report needs a lineage: --lineage <tsv>, or -D <database directory> with ../taxonomy next to it.");
+  if (!db.empty() && db.back() != '/') db.push_back('/');
+  // --rank-report: the lineage over the labels of the first file's header, the counters, the per-read scratch
+  const bool ranks = !rank_report.empty();
+  const std::string tail = ",Length,Gamma,1st_assignment,score1,2nd_assignment,score2,confidence";
+  std::vector<std::string> ru_labels;
+  mic::rank::Lineage lin;
+  std::vector<uint64_t> ru_counts, ru_tot;
+  std::vector<uint32_t> ru_off, ru_tg, ru_cn, ru_touched;
 
   std::map<std::string, uint64_t> per_label;
   uint64_t unassigned = 0, filtered = 0;
@@ -122,7 +144,34 @@ int main(int argc, char** argv) {
       ++ln;
       if (!line.empty() && line.back() == '\r') line.pop_back();
       if (line.empty()) continue;
-      if (ln == 1 && line.compare(0, 10, "Object_ID,") == 0) continue;      // header
+      if (ln == 1 && line.compare(0, 10, "Object_ID,") == 0) {                // header
+        if (ranks) {
+          std::vector<std::string> labs;
+          if (line.size() > 9 + tail.size() && line.compare(line.size() - tail.size(), tail.size(), tail) == 0) {
+            const std::string mid = line.substr(10, line.size() - tail.size() - 10);
+            for (size_t a = 0;;) { const size_t b = mid.find(',', a); labs.push_back(mid.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
+          }
+          if (labs.empty()) { std::cerr << "--rank-report needs the per-target counts of an --extended result file; " << path << " is not one." << std::endl; return 1; }
+          if (ru_labels.empty()) {
+            ru_labels = labs;
+            std::string err;
+            bool ok;
+            if (!lineage_file.empty()) ok = mic::rank::lineage_from_file(lineage_file, ru_labels, lin, err);
+            else {
+              mic::abund::Taxonomy t;
+              if (!mic::rank::load_taxonomy(db + "../taxonomy", t)) { std::cerr << "--rank-report: no taxonomy (nodes.dmp) in " << db << "../taxonomy and no --lineage <tsv>." << std::endl; return 1; }
+              ok = mic::rank::lineage_from_taxonomy(ru_labels, t, lin, err);
+            }
+            if (!ok) { std::cerr << err << std::endl; return 1; }
+            ru_counts.assign(lin.n_counters(), 0);
+            ru_off.assign(8, 0);
+            for (uint32_t l = 1; l <= lin.n_levels; ++l) ru_off[l] = ru_off[l - 1] + (uint32_t)lin.groups[l - 1].size();
+            ru_tot.assign(ru_labels.size(), 0); ru_touched.assign(ru_labels.size(), 0);
+          } else if (labs != ru_labels) { std::cerr << "--rank-report: " << path << " has other targets than " << files[0] << "." << std::endl; return 1; }
+        }
+        continue;
+      }
+      if (ranks && ru_labels.empty()) { std::cerr << "--rank-report needs the header line of an --extended result file; " << path << " has none." << std::endl; return 1; }
       // the last seven fields (the object name may hold commas)
       std::string fld[7];
       size_t end = line.size();
@@ -139,9 +188,24 @@ int main(int argc, char** argv) {
         return 1;
       }
       const std::string& first = fld[2];
+      const bool gamma = decimal_at_least(fld[1], f.gamma_num, f.gamma_den);
+      if (ranks) {      // the T count columns in front of the last seven
+        ru_tg.clear(); ru_cn.clear();
+        for (size_t t = ru_labels.size(); t-- > 0 && ok;) {
+          const size_t c = end == 0 ? std::string::npos : line.rfind(',', end - 1);
+          uint64_t v = 0;
+          if (c == std::string::npos || !parse_u32(line.substr(c + 1, end - c - 1), v)) { ok = false; break; }
+          if (v) { ru_tg.push_back((uint32_t)t); ru_cn.push_back((uint32_t)v); }
+          end = c;
+        }
+        if (!ok) { std::cerr << "Failed to read line " << ln << " of " << path << ": not a line of an --extended result file with " << ru_labels.size() << " targets." << std::endl; return 1; }
+        std::reverse(ru_tg.begin(), ru_tg.end()); std::reverse(ru_cn.begin(), ru_cn.end());
+        uint32_t row[MIC_ROLLUP_WORDS];
+        ++ru_counts[mic_rollup_read_host(ru_tg.data(), ru_cn.data(), ru_tg.size(), (uint32_t)ru_labels.size(), lin.n_levels, lin.group_of.data(), ru_off.data(),
+                                         0, 0, f, gamma ? 1 : 0, 0, ru_tot.data(), ru_touched.data(), row, nullptr)];
+      }
       if (first == "NA") { ++unassigned; continue; }
       const bool conf = s1 * f.conf_den >= f.conf_num * (s1 + s2);
-      const bool gamma = decimal_at_least(fld[1], f.gamma_num, f.gamma_den);
       if (conf && gamma) ++per_label[first];
       else ++filtered;
     }
@@ -150,9 +214,12 @@ int main(int argc, char** argv) {
   std::vector<uint64_t> counts = {unassigned, filtered};
   for (const auto& kv : per_label) { labels.push_back(kv.first); counts.push_back(kv.second); }
   mic::abund::Taxonomy tax;
-  if (!db.empty()) {
-    if (db.back() != '/') db.push_back('/');
-    mic::abund::load_taxonomy(db + "../taxonomy", tax);
+  if (!db.empty()) mic::abund::load_taxonomy(db + "../taxonomy", tax);
+  if (ranks) {
+    if (ru_labels.empty()) { std::cerr << "--rank-report: no result line was read." << std::endl; return 1; }
+    const std::string report = mic::rank::format_report(ru_counts, lin);
+    FILE* out = fopen(rank_report.c_str(), "wb");
+    if (!out || fwrite(report.data(), 1, report.size(), out) != report.size() || fclose(out) != 0) { std::cerr << "Failed to write the rank report: " << rank_report << std::endl; return 1; }
   }
   const std::string table = mic::abund::format_table(counts, labels, &tax, a_num, a_den);
   if (fwrite(table.data(), 1, table.size(), stdout) != table.size() || fflush(stdout) != 0) { std::cerr << "Failed to write the table." << std::endl; return 1; }

@@ -477,3 +477,50 @@ int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t*
   return mic_abund_parse_text(text, max_int, num, den) ? MIC_OK : MIC_E_INVALID;
 }
 }  // extern "C"
+
+// ---- rank roll-up: the rule of mic_rollup.h on the CPU (batches the host path classifies, estimate_abundance's cross-check) --------
+#include "mic_rollup.h"
+
+extern "C" int mic_rollup_host(const uint32_t* rows, uint32_t row_words, const uint32_t* dense, const uint32_t* norm, size_t n_reads, int k,
+                               uint32_t n_targets, uint32_t n_levels, const uint16_t* group_of, const mic_abund_filter* filter,
+                               uint32_t* rollup, uint32_t* levels, uint64_t* counts) {
+  if (!filter || (!rows && !dense && n_reads) || (rows && row_words < 2)) return MIC_E_INVALID;
+  if (!mic_abund_filter_ok(*filter) || (!norm && filter->gamma_num)) return MIC_E_INVALID;
+  if (mic_rollup_check_lineage(n_targets, n_levels, group_of, nullptr, nullptr) != 0) return MIC_E_INVALID;
+  const uint32_t T = n_targets, L = n_levels;
+  uint32_t off[8] = {0}, n_groups[8] = {T};
+  for (uint32_t l = 1; l <= L; ++l) {
+    const uint16_t* g = group_of + (size_t)(l - 1) * T;
+    uint32_t G = 0;
+    for (uint32_t t = 0; t < T; ++t) if (g[t] >= G) G = g[t] + 1u;
+    n_groups[l] = G; off[l] = off[l - 1] + n_groups[l - 1];
+  }
+  std::vector<uint64_t> tot(T, 0);
+  std::vector<uint32_t> tg, cn, touched(T);
+  for (size_t r = 0; r < n_reads; ++r) {
+    const uint32_t* row = rows ? rows + r * row_words : nullptr;
+    uint32_t* out = rollup ? rollup + r * MIC_ROLLUP_WORDS : nullptr;
+    uint32_t* lev = levels ? levels + r * (size_t)(L + 1) * 4 : nullptr;
+    const bool use_dense = !row || row[0] > row_words - 1;
+    if (use_dense && !dense) {
+      if (out) { memset(out, 0, MIC_ROLLUP_WORDS * 4); out[5] = MIC_ROLLUP_PENDING; out[6] = MIC_FLAG_ROW_OVERFLOW; }
+      if (lev) memset(lev, 0, (size_t)(L + 1) * 16);
+      continue;
+    }
+    tg.clear(); cn.clear();
+    if (use_dense) {
+      const uint32_t* d = dense + r * (size_t)T;
+      for (uint32_t t = 0; t < T; ++t) if (d[t]) { tg.push_back(t); cn.push_back(d[t]); }
+    } else {
+      for (uint32_t e = 0; e < row[0]; ++e) {
+        const uint32_t t = row[1 + e] & 0xFFFF, c = row[1 + e] >> 16;
+        if (t < T && c) { tg.push_back(t); cn.push_back(c); }
+      }
+    }
+    uint32_t tmp[MIC_ROLLUP_WORDS];
+    const uint32_t bucket = mic_rollup_read_host(tg.data(), cn.data(), tg.size(), T, L, group_of, off, norm ? norm[r] : 0u, k, *filter, -1,
+                                                 use_dense ? MIC_FLAG_DENSE_PATH : 0u, tot.data(), touched.data(), out ? out : tmp, lev);
+    if (counts) ++counts[bucket];
+  }
+  return MIC_OK;
+}

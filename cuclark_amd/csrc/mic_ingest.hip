@@ -36,6 +36,7 @@ int mic_set_error(int code, const char* fmt, ...);
 int mic_bind_thread_near_device(int device, int on);
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
 MicAbund* mic_engine_abund(mic_engine* e);
+MicRollup* mic_engine_rollup(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
 bool mic_peer_enable(int from, int to);
 
@@ -502,6 +503,10 @@ struct Slot {
   hipEvent_t ev = nullptr, ev_up = nullptr, ev_k = nullptr;
   uint32_t n_reads = 0, cont_used = 0;
   std::vector<void*> dev_allocs, host_allocs;
+  // rank roll-up (mic_rollup_start on the slot's engine; allocated with the first such batch): the sparse rows of the batch, ru_row_words
+  // u32 per read, their roll-up rows, and the pinned copy of those when the slots were allocated with want_results
+  uint32_t* d_ru_rows = nullptr; uint32_t* d_rollup = nullptr; uint32_t* h_rollup = nullptr;
+  uint32_t ru_row_words = 0; bool ru_valid = false;
   // table-sharded batches (mic_ingest_classify_group): what this slot keeps on every engine of its group, the owner included
   struct Peer {
     mic_engine* eng = nullptr; int device = 0;
@@ -664,6 +669,27 @@ void free_ingest(Ingest* g) {
   delete g;
 }
 
+// the slot's roll-up buffers for rows of rw words (a slot that changes between single-engine and table-sharded batches gets new ones)
+int ensure_rollup_buffers(Ingest* g, Slot& s, uint32_t rw) {
+  if (s.d_rollup && s.ru_row_words == rw) return MIC_OK;
+  const size_t n = g->max_reads + 1;
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, n * ((size_t)rw + MIC_ROLLUP_WORDS) * 4 + 512);
+  if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: roll-up rows of %u words for %zu reads: %s", rw, n, hipGetErrorString(e));
+  s.dev_allocs.push_back(d);
+  s.d_rollup = (uint32_t*)d;
+  s.d_ru_rows = (uint32_t*)((char*)d + ((n * MIC_ROLLUP_WORDS * 4 + 255) & ~(size_t)255));
+  s.ru_row_words = rw;
+  if (g->want_results && !s.h_rollup) {
+    void* h = nullptr;
+    e = hipHostMalloc(&h, n * MIC_ROLLUP_WORDS * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: pinned roll-up rows: %s", hipGetErrorString(e));
+    s.host_allocs.push_back(h);
+    s.h_rollup = (uint32_t*)h;
+  }
+  return MIC_OK;
+}
+
 double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec / 1e9; }
 
 // ---- table-sharded batches: the slot's buffers on the engines of its group, and the exchange ------------------------------
@@ -782,7 +808,7 @@ int setup_peers(Ingest* g, Slot& s, mic_engine* const* group, size_t P, size_t o
 // Every engine of the group probes the batch's packed reads (on the owner's device after pack_kernel) against its part; the rows
 // are summed read-range owned; the owner's d_results hold best / second-best of all reads when its stream has passed the waits
 // queued here.  Nothing blocks the host.
-int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* g, Slot& s, uint32_t n, uint32_t nb, int k) {
+int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* g, Slot& s, uint32_t n, uint32_t nb, int k, uint32_t* d_merged) {
   const size_t rw = kGroupRowWords;
   Slot::Peer& O = s.peers[owner];
   // containers the packer can have written for nb bytes in n reads (record_kernel's reservations) + what the kernel reads ahead
@@ -846,6 +872,10 @@ int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* 
         ITRY(hipMemcpyPeerAsync(O.d_res + lo * 8, O.device, q.d_res, q.device, len * 32, q.stream));
         s.x_bytes += len * 32;
       }
+      if (d_merged) {        // roll-up: the summed rows of the range go to the owner as well (64 bytes a read next to the 32 of its result)
+        ITRY(hipMemcpyPeerAsync(d_merged + lo * rw, O.device, cur, q.device, len * rw * 4, q.stream));
+        if (j != owner) s.x_bytes += len * rw * 4;
+      }
     }
     if (timed) ITRY(hipEventRecord(q.tv[4], q.stream));
     ITRY(hipEventRecord(q.ev_done, q.stream));
@@ -857,7 +887,7 @@ int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* 
   return MIC_OK;
 }
 
-int group_query(mic_engine* const* group, size_t P, size_t owner, Ingest* g, Slot& s, uint32_t n, uint32_t nb, int k) {
+int group_query(mic_engine* const* group, size_t P, size_t owner, Ingest* g, Slot& s, uint32_t n, uint32_t nb, int k, uint32_t* d_merged) {
   // the slot's buffers on the engines of its group are kept from batch to batch while the group is the same: the same engines in the
   // same order, each on the device and with the table it had (an engine destroyed and another created at its address is not the same)
   bool same = s.peers.size() == P && s.group_owner == owner && s.timed == group_timing();
@@ -867,7 +897,7 @@ int group_query(mic_engine* const* group, size_t P, size_t owner, Ingest* g, Slo
            dev == s.peers[p].device && (const void*)t.slots == s.peers[p].table_id;
   }
   if (!same) { int rc = setup_peers(g, s, group, P, owner); if (rc) { free_peers(s); return rc; } }
-  const int rc = group_query_issue(group, P, owner, g, s, n, nb, k);
+  const int rc = group_query_issue(group, P, owner, g, s, n, nb, k, d_merged);
   if (rc) {
     // an error in the middle leaves work queued on the helpers' streams that reads and writes the slot's buffers: wait for it
     // before the caller reuses or frees them (the error text is kept)
@@ -1017,6 +1047,7 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
   ITRY(hipSetDevice(dev));
   Slot& s = g->slots[slot_id];
+  s.ru_valid = false;
   memset(out, 0, sizeof(*out));
   const bool resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
   const uint8_t first = resident ? (uint8_t)((flags & MIC_INGEST_RESIDENT_FASTQ) == MIC_INGEST_RESIDENT_FASTQ ? '@' : '>') : s.h_raw[0];
@@ -1071,16 +1102,22 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     if (blocks > cap) blocks = cap;
     pack_kernel<<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k);
   }
+  // rank roll-up started on the slot's engine: the rows instantiation of the same kernel fills the slot's row buffer.  One engine:
+  // rows of the --extended width, so that a batch is handed back exactly when it is handed back without roll-up (a row that does
+  // not fit is a read of more than 64 targets, which the kernel flags anyway); a group: the summed rows, kGroupRowWords wide.
+  MicRollup& ru = *mic_engine_rollup(e);
+  const bool roll = ru.on && ru.d_counts && ru.n_levels;
+  if (roll && (rc = ensure_rollup_buffers(g, s, n_group == 1 ? std::min<uint32_t>(nt + 1, 65u) : kGroupRowWords))) return rc;
   if (n_group == 1) {
     ITRY(hipMemsetAsync(s.d_flagged, 0, 4, st));
     MicQueryArgs qa;
-    qa.t = t; qa.reads_ptr = s.d_rp; qa.cont = s.d_cont; qa.n_reads = n_reads; qa.row_words = 0; qa.results = s.d_results;
-    qa.rows = nullptr; qa.flagged = s.d_flagged; qa.flagged_cap = kFlaggedCapI;
+    qa.t = t; qa.reads_ptr = s.d_rp; qa.cont = s.d_cont; qa.n_reads = n_reads; qa.row_words = roll ? s.ru_row_words : 0; qa.results = s.d_results;
+    qa.rows = roll ? s.d_ru_rows : nullptr; qa.flagged = s.d_flagged; qa.flagged_cap = kFlaggedCapI;
     mic_crowd_attach(qa, s.d_crowd, g->max_reads / 4 + 64);
     ITRY(mic_launch_query(qa, sc, ncu, st));
   } else {
     // table-sharded: all engines of the group probe the batch against their parts, the rows are summed read-range owned
-    if ((rc = group_query(group, n_group, owner, g, s, n_reads, nb, k))) return rc;
+    if ((rc = group_query(group, n_group, owner, g, s, n_reads, nb, k, roll ? s.d_ru_rows : nullptr))) return rc;
     ITRY(hipSetDevice(dev));
   }
   CsvArgs ca;
@@ -1101,6 +1138,11 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     if (ab.on && ab.d_counts && ab.n_words == nt + 2)
       ITRY(mic_launch_abund(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ab, ab.d_counts, s.d_hdr + H_STATUS, st));
   }
+  if (roll) {  // the same guard: nothing of a batch that is handed back is counted here
+    ITRY(mic_launch_rollup(ru, s.d_ru_rows, s.ru_row_words, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ru.filter, s.d_rollup, nullptr,
+                           ru.d_counts, s.d_hdr + H_STATUS, st));
+    if (s.h_rollup) ITRY(hipMemcpyAsync(s.h_rollup, s.d_rollup, (size_t)n_reads * MIC_ROLLUP_WORDS * 4, hipMemcpyDeviceToHost, st));
+  }
   if (no_csv && g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, st));
   ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));
   ITRY(hipEventRecord(s.ev, st));
@@ -1112,6 +1154,7 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   uint32_t status = s.h_hdr[H_STATUS];
   if (csv_bytes > g->csv_cap || s.h_hdr[H_CONT] > g->cont_cap) status |= MIC_INGEST_TOO_MANY;
   if (status) { out->status = MIC_INGEST_FALLBACK | status; return MIC_OK; }
+  s.ru_valid = roll && s.h_rollup;
   if (no_csv) {
     out->n_reads = n_reads; out->csv_bytes = 0; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
     out->status = MIC_INGEST_OK;
@@ -1135,6 +1178,16 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+lengths %.0f us, csv %.0f us\n", slot_id, nb, n_reads,
             (t1 - t0) * 1e6, (t2 - t1) * 1e6, (t3 - t2) * 1e6);
   }
+  return MIC_OK;
+}
+
+int mic_ingest_rollup_rows(mic_engine* e, size_t slot_id, const uint32_t** rollup, uint64_t* n_reads) {
+  if (!e || !rollup || !n_reads) return mic_set_error(MIC_E_INVALID, "null argument");
+  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
+  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  const Slot& s = g->slots[slot_id];
+  if (!s.ru_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no roll-up rows (mic_rollup_start, want_results, MIC_INGEST_OK)");
+  *rollup = s.h_rollup; *n_reads = s.n_reads;
   return MIC_OK;
 }
 

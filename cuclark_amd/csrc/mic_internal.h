@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "mi_clark.h"
+
 // ---- exact 64-bit division by a runtime-constant divisor (HTSIZE) -------------------------------
 // Granlund–Montgomery "round-up" magic, computed once on the host (mic_make_div):
 //   magic == 0 : divisor is a power of two, q = n >> shift
@@ -226,5 +228,28 @@ struct MicAbund {
 // status != nullptr: a non-zero *status (the batch is handed back) makes the launch add nothing
 hipError_t mic_launch_abund(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
                             const MicAbund& f, unsigned long long* counts, const uint32_t* status, hipStream_t s);
+
+// ---- rank roll-up (mic_rollup.hip; the rule: mic_rollup.h) ------------------------------------------------------------------------
+// An engine's lineage (mic_rollup_set) and, while mic_rollup_start is in force, its counters.  The lineage's device arrays are one
+// allocation (d_block).
+struct MicRollup {
+  uint32_t n_levels = 0;            // 0: no lineage set
+  uint32_t n_groups[8] = {};        // [0] = num_targets
+  uint32_t off[8] = {};             // counter of group g at level l: 2 + off[l] + g
+  uint32_t seg_off[8] = {};         // d_seg + seg_off[l]: the n_groups[l] + 1 segment starts of level l (l >= 1)
+  uint32_t n_counters = 0;
+  void* d_block = nullptr;
+  const uint16_t* d_group_of = nullptr;   // [n_levels][T]
+  const uint16_t* d_perm = nullptr;       // [n_levels][T]: the targets sorted by their group at level l (stable)
+  const uint32_t* d_seg = nullptr;
+  unsigned long long* d_counts = nullptr; // n_counters u64 (mic_rollup_start)
+  bool on = false;
+  mic_abund_filter filter = {5, 10, 0, 1};
+};
+// rows form: reads [0, n) of `rows` (row_words u32 each) -> rollup (8 u32 each), levels (optional), counts (optional, added to);
+// norm of read r = norm[r] - norm_sub (norm == nullptr: 0); status as for mic_launch_abund
+hipError_t mic_launch_rollup(const MicRollup& ru, const uint32_t* rows, uint32_t row_words, const uint32_t* norm, uint32_t norm_sub, size_t n,
+                             int k, uint32_t n_targets, const mic_abund_filter& f, uint32_t* rollup, uint32_t* levels,
+                             unsigned long long* counts, const uint32_t* status, hipStream_t s);
 
 #endif

@@ -364,6 +364,60 @@ class MiClarkDB:
         f = filt if filt is not None else host.abund_filter()
         check(self.L.mic_abundance_device(self.h, d_results, d_norm or None, n_reads, C.byref(f), d_counts, stream or None))
 
+    # -- rank roll-up (mic_rollup_*): a lineage is u16[n_levels, num_targets], level 1 first (host.rollup_check: its two conditions)
+    def rollup_set(self, group_of):
+        """Install a lineage on the engine (None or an empty array clears it)."""
+        if group_of is None or np.asarray(group_of).size == 0:
+            check(self.L.mic_rollup_set(self.h, 0, None))
+            return
+        g = np.ascontiguousarray(group_of, np.uint16).reshape(-1, self.num_targets)
+        check(self.L.mic_rollup_set(self.h, g.shape[0], g.ctypes.data))
+
+    def rollup_layout(self):
+        """(n_groups u32[n_levels + 1] with n_groups[0] = num_targets, number of counters)."""
+        ng = np.zeros(8, np.uint32)
+        nc = C.c_uint64(0)
+        rc = self.L.mic_rollup_layout(self.h, ng.ctypes.data, C.byref(nc))
+        if rc < 0:
+            check(rc)
+        return ng[: rc + 1].copy(), int(nc.value)
+
+    def rollup_device(self, d_rows, d_norm, n_reads, d_rollup, d_levels=0, d_counts=0, filt=None, stream=0):
+        """Sparse rows (row_words u32 per read) in device memory -> roll-up rows (u32[n, 8]), optional per-level results
+        (u32[n, n_levels + 1, 4]), counters ADDED to d_counts (u64[rollup_layout()[1]]); pointers as for abundance_device."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_rollup_device(self.h, d_rows, d_norm or None, n_reads, C.byref(f), d_rollup, d_levels or None, d_counts or None,
+                                       stream or None))
+
+    def rollup_dense_device(self, d_dense, d_ids, n_ids, d_norm, d_rollup, d_levels=0, d_counts=0, filt=None, stream=0):
+        """The same from dense counts (u32[n_ids, num_targets]): completes roll-up row / levels d_ids[i] (i when d_ids is 0)."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_rollup_dense_device(self.h, d_dense, d_ids or None, n_ids, d_norm or None, C.byref(f), d_rollup, d_levels or None,
+                                             d_counts or None, stream or None))
+
+    def rollup_start(self, filt=None):
+        """Zero and enable the engine's roll-up counters: every ingest batch that returns MIC_INGEST_OK adds its reads."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_rollup_start(self.h, C.byref(f)))
+
+    def rollup_fetch(self):
+        """u64[2 + T + G_1 + .. + G_L]: [0] no hit, [1] unresolved, [2 + off_l + g] group g of level l (waits for the device)."""
+        out = np.zeros(self.rollup_layout()[1], np.uint64)
+        check(self.L.mic_rollup_fetch(self.h, out.ctypes.data, out.size))
+        return out
+
+    def rollup_stop(self):
+        check(self.L.mic_rollup_stop(self.h))
+
+    def ingest_rollup_rows(self, slot):
+        """u32[n, 8]: the roll-up rows of the slot's last MIC_INGEST_OK batch (roll-up started, slots allocated with want_results)."""
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        check(self.L.mic_ingest_rollup_rows(self.h, slot, C.byref(p), C.byref(n)))
+        return _as_np(p.value, (int(n.value), _lib.MIC_ROLLUP_WORDS), np.uint32).copy()
+
     def ingest_fetch_group_rows(self, slot, part):
         """test hook: the partial rows engine `part` of the group computed for the slot's last table-sharded batch"""
         n, rw = C.c_uint64(0), C.c_uint32(0)

@@ -120,3 +120,43 @@ def abundance_host(results, norm, k, n_targets, filt=None):
     if rc != 0:
         raise ValueError(f"mic_abundance_host: invalid argument ({rc})")
     return counts
+
+
+def rollup_check(n_targets, group_of):
+    """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
+    1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""
+    L = _lib.load()
+    g = np.ascontiguousarray(group_of, np.uint16)
+    n_levels = g.size // int(n_targets) if int(n_targets) and g.size % int(n_targets) == 0 else 0
+    if L.mic_rollup_check(int(n_targets), n_levels, g.ctypes.data if g.size else None) != 0:
+        raise ValueError(L.mic_last_error().decode(errors="replace"))
+
+
+def rollup_host(rows, norm, k, n_targets, group_of, filt=None, dense=None, want_levels=False):
+    """mic_rollup_host: the roll-up rule of csrc/mic_rollup.h on the CPU.  rows: u32[n, row_words] sparse rows or None; dense:
+    u32[n, n_targets] counts or None (used for the reads whose row is invalid; for all reads when rows is None).
+    Returns (rollup u32[n, 8], levels u32[n, n_levels + 1, 4] or None, counts u64[2 + T + G_1 + .. + G_L])."""
+    L = _lib.load()
+    T = int(n_targets)
+    g = np.ascontiguousarray(group_of, np.uint16).reshape(-1, T)
+    nl = g.shape[0]
+    rw = 0
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, np.uint32)
+        rw = rows.shape[1]
+        n = rows.shape[0]
+    if dense is not None:
+        dense = np.ascontiguousarray(dense, np.uint32).reshape(-1, T)
+        n = dense.shape[0]
+    nm = np.ascontiguousarray(norm, np.uint32) if norm is not None else None
+    n_counters = 2 + T + sum(int(g[l].max()) + 1 for l in range(nl))
+    rollup = np.zeros((n, _lib.MIC_ROLLUP_WORDS), np.uint32)
+    levels = np.zeros((n, nl + 1, 4), np.uint32) if want_levels else None
+    counts = np.zeros(n_counters, np.uint64)
+    f = filt if filt is not None else abund_filter()
+    rc = L.mic_rollup_host(rows.ctypes.data if rows is not None else None, rw, dense.ctypes.data if dense is not None else None,
+                           nm.ctypes.data if nm is not None else None, n, int(k), T, nl, g.ctypes.data, C.byref(f),
+                           rollup.ctypes.data, levels.ctypes.data if levels is not None else None, counts.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_rollup_host: invalid argument ({rc})")
+    return rollup, levels, counts

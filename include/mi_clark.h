@@ -455,6 +455,56 @@ int mic_abundance_host(const uint32_t* results, const uint32_t* norm, size_t n_r
                        const mic_abund_filter* filter, uint64_t* counts);
 int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t* den);
 
+/* ---- rank roll-up: every read resolved at the lowest confident level of a lineage (csrc/mic_rollup.h: the rule) ---------------
+ * A lineage has n_levels (1 .. MIC_ROLLUP_MAX_LEVELS) levels above the targets: group_of[(l - 1) * num_targets + t] is the group of
+ * target t at level l; level 0 is the targets themselves.  Ids at every level are numbered by first appearance in ascending target
+ * order, and level l is a coarsening of level l - 1 (mic_rollup_check; MIC_E_INVALID otherwise).  A read's per-target counts (its
+ * sparse row, or dense counts when the row did not fit) are summed per group, best / second-best are taken at every level by
+ * resultKernel's rule, and the read is assigned at the LOWEST level whose confidence best / (best + second) passes the filter (gamma
+ * as for mic_abundance_*: the same at every level).
+ *   roll-up row  MIC_ROLLUP_WORDS u32: {sum, idxBest, best, idxSecond, second, level, flags, nGroupsHit}: indices are group + 1 at
+ *                `level` (0 = none); no level passes: level = MIC_ROLLUP_UNRESOLVED, words 1-4 and 7 are level 0's; sum == 0: all
+ *                zero; the sparse row is MIC_ROW_INVALID: level = MIC_ROLLUP_PENDING, flags = MIC_FLAG_ROW_OVERFLOW, nothing is
+ *                counted and mic_rollup_dense_device (or mic_rollup_host with dense counts) completes the read.
+ *   levels       optional, (n_levels + 1) * 4 u32 per read: {idxBest, best, idxSecond, second} of every level, level 0 first: the
+ *                read classified at each rank.
+ *   counters     u64 [2 + T + G_1 + .. + G_L] (mic_rollup_layout): [0] no hit, [1] unresolved, [2 + off_l + g] reads assigned
+ *                to group g of level l, off_0 = 0, off_l = T + G_1 + .. + G_(l-1).  Every counted read adds one to exactly one.
+ * mic_rollup_check         host only: MIC_OK or MIC_E_INVALID (mic_last_error names the level and the target).
+ * mic_rollup_set           checks and installs a lineage on the engine (n_levels == 0 clears it); not while roll-up is started.
+ * mic_rollup_layout        n_groups[0 .. n_levels] (n_groups[0] = num_targets) and the number of counters; either may be NULL.
+ *                          Returns the number of levels (>= 1) or a negative code.
+ * mic_rollup_device        sparse rows (the engine's row_words u32 per read) -> roll-up rows, optional levels, counters ADDED to
+ *                          d_counts (optional).  d_norm as for mic_abundance_device.  Asynchronous on `stream`.
+ * mic_rollup_dense_device  the same from dense counts (u32 [n_ids * num_targets], mic_count_dense_device's): writes roll-up row
+ *                          and levels d_ids[i] (i when d_ids is NULL), flags = MIC_FLAG_DENSE_PATH; d_norm is indexed like them.
+ * mic_rollup_host          the rule on the CPU, no device needed.  rows: row_words u32 per read; dense (optional): num_targets u32
+ *                          per read, used for the reads whose row is MIC_ROW_INVALID (rows == NULL: for every read); without it
+ *                          such reads come back MIC_ROLLUP_PENDING and uncounted.  rollup / levels / counts are optional.
+ * mic_rollup_start / _fetch / _stop   the engine's counters over ingest batches, by the contract of mic_abundance_start / _fetch /
+ *                          _stop: every batch that returns MIC_INGEST_OK adds its reads on the device, a batch handed back adds
+ *                          nothing.  While started, a batch with a read whose row does not fit is handed back with
+ *                          MIC_INGEST_DENSE.  mic_ingest_rollup_rows: the roll-up rows of the slot's last MIC_INGEST_OK batch
+ *                          (pinned host memory, valid until the slot's next call) when the slots were allocated with want_results. */
+#define MIC_ROLLUP_WORDS 8
+#define MIC_ROLLUP_MAX_LEVELS 7
+#define MIC_ROLLUP_UNRESOLVED 0xFFFFFFFFu
+#define MIC_ROLLUP_PENDING 0xFFFFFFFEu
+int mic_rollup_check(uint32_t n_targets, uint32_t n_levels, const uint16_t* group_of);
+int mic_rollup_set(mic_engine* e, uint32_t n_levels, const uint16_t* group_of);
+int mic_rollup_layout(const mic_engine* e, uint32_t* n_groups, uint64_t* n_counters);
+int mic_rollup_device(mic_engine* e, const uint32_t* d_rows, const uint32_t* d_norm, size_t n_reads, const mic_abund_filter* filter,
+                      uint32_t* d_rollup, uint32_t* d_levels, uint64_t* d_counts, void* stream);
+int mic_rollup_dense_device(mic_engine* e, const uint32_t* d_dense, const uint32_t* d_ids, size_t n_ids, const uint32_t* d_norm,
+                            const mic_abund_filter* filter, uint32_t* d_rollup, uint32_t* d_levels, uint64_t* d_counts, void* stream);
+int mic_rollup_host(const uint32_t* rows, uint32_t row_words, const uint32_t* dense, const uint32_t* norm, size_t n_reads, int k,
+                    uint32_t n_targets, uint32_t n_levels, const uint16_t* group_of, const mic_abund_filter* filter,
+                    uint32_t* rollup, uint32_t* levels, uint64_t* counts);
+int mic_rollup_start(mic_engine* e, const mic_abund_filter* filter);
+int mic_rollup_fetch(mic_engine* e, uint64_t* counts, size_t n);
+int mic_rollup_stop(mic_engine* e);
+int mic_ingest_rollup_rows(mic_engine* e, size_t slot, const uint32_t** rollup, uint64_t* n_reads);
+
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */
 int mic_format_ratio_g(uint32_t num, uint32_t den, char* out16);
