@@ -56,6 +56,7 @@ class MicIngestResult(C.Structure):
 
 MIC_INGEST_OK, MIC_INGEST_FALLBACK, MIC_INGEST_ODD_RECORD, MIC_INGEST_TRUNCATED = 0, 1, 2, 4
 MIC_INGEST_LONG_READ, MIC_INGEST_TOO_MANY, MIC_INGEST_DENSE = 8, 16, 32
+MIC_INGEST_FASTQ_2LINE = 2      # ingest flag: FASTQ records of header + sequence line only
 MIC_INGEST_NO_CSV = 16          # ingest flag (not a status bit): no CSV kernels, no text back
 
 
@@ -111,6 +112,8 @@ SYMBOLS = [
     ("mic_ingest_group_stats", C.c_int, [_VP, C.POINTER(C.c_double), _SZ]),
     ("mic_ingest_fetch_packed", C.c_int, [_VP, _SZ, _VP, _SZ, _VP, _SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("mic_ingest_free", C.c_int, [_VP]),
+    ("mic_ingest_set_min_quality", C.c_int, [_VP, C.c_uint32]),
+    ("mic_fastq_mask_quality", C.c_int, [_VP, _SZ, C.c_uint32, _VP]),
     ("mic_gz_inflate_device", C.c_int, [_VP, _VP, _SZ, C.POINTER(_VP), C.POINTER(_SZ), C.POINTER(C.c_uint32)]),
     ("mic_gz_copy_text", C.c_int, [_VP, _VP, _SZ, _SZ, _VP]),
     ("mic_gz_free_text", C.c_int, [_VP, _VP]),

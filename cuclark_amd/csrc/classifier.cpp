@@ -198,6 +198,8 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     check(mic_create(&cfg, &e), "engine creation");
     engines_.push_back(e);
     if (parts_ > 1) check(mic_db_set_part(e, (uint32_t)(d % parts_), (uint32_t)parts_), "table part");
+    // --min-base-quality: every engine masks on its device - in the packer for four-line FASTQ, in the pair merge for two inflated mates
+    if (opt_.min_quality_byte) check(mic_ingest_set_min_quality(e, opt_.min_quality_byte), "base-quality threshold");
   }
   if (use > 1) {
     std::cerr << "Devices: " << use << " engine(s) on " << nd_used << " device(s)";
@@ -327,8 +329,8 @@ void Classifier::parse_targets() {
   names_.insert(names_.end(), labels_c_.begin(), labels_c_.end());
 }
 
-std::string merge_paired(const std::string& file1, const std::string& file2) {
-  PairedSource src(file1, file2, ~(size_t)0 >> 1);
+std::string merge_paired(const std::string& file1, const std::string& file2, uint32_t min_quality_byte) {
+  PairedSource src(file1, file2, ~(size_t)0 >> 1, min_quality_byte);
   if (!src.ok()) die("Error: Found read without sequence");
   Classifier::Segment s;
   std::string out;
@@ -336,8 +338,9 @@ std::string merge_paired(const std::string& file1, const std::string& file2) {
   return out;
 }
 
-bool merge_paired_parallel(const std::string& file1, const std::string& file2, unsigned threads, size_t batch_bytes, std::string& out) {
-  PairedFileFeeder feed(file1, file2, threads);
+bool merge_paired_parallel(const std::string& file1, const std::string& file2, unsigned threads, size_t batch_bytes, std::string& out,
+                           uint32_t min_quality_byte) {
+  PairedFileFeeder feed(file1, file2, threads, min_quality_byte);
   if (!feed.ok()) return false;
   out.clear();
   Classifier::Range r;
@@ -489,7 +492,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
         prelude_s_ = (tb.tv_sec - ta.tv_sec) + (tb.tv_usec - ta.tv_usec) / 1e6;
         if (getenv("MIC_CLI_TIMING")) std::cerr << "[timing] inflate: " << ((ga ? ia.size() : 0) + (gb ? ib.size() : 0)) / 1e6 << " MB of text in " << prelude_s_ * 1e3
                                                 << " ms (" << th << " threads per file)" << std::endl;
-        PairedFileFeeder feed(ga ? ia.path() : a, gb ? ib.path() : b, (unsigned)opt_.threads);
+        PairedFileFeeder feed(ga ? ia.path() : a, gb ? ib.path() : b, (unsigned)opt_.threads, opt_.min_quality_byte);
         const bool done = feed.ok() && run_stream(feed, res, true, (size_t)feed.merged_estimate());
         prelude_s_ = 0;
         if (done) return;
@@ -498,10 +501,10 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
     if (device_ingest() && !is_gzip(a) && !is_gzip(b) && !getenv("MIC_SERIAL_PAIRS")) {
       // two plain FASTQ files: the loaders merge the pair in parallel; files that need the reference's line-by-line
       // treatment come back here
-      PairedFileFeeder feed(a, b, (unsigned)opt_.threads);
+      PairedFileFeeder feed(a, b, (unsigned)opt_.threads, opt_.min_quality_byte);
       if (feed.ok() && run_stream(feed, res, true, (size_t)feed.merged_estimate())) return;
     }
-    PairedSource src(a, b, segment_bytes_);
+    PairedSource src(a, b, segment_bytes_, opt_.min_quality_byte);
     if (!src.ok()) { std::cerr << "Failed to open " << merged_name << std::endl; return; }
     if (device_ingest()) { SegmentFeeder feed(src); run_stream(feed, res, true, ~(size_t)0 >> 1); }
     else run_segments(src, res, true);

@@ -36,6 +36,7 @@ struct Options {
   std::string abundance;                                     // --abundance <file>: the abundance profile is counted (mic_abundance_*)
   mic_abund_filter abund_filter = {5, 10, 0, 1};             // --min-confidence / --min-gamma / --highconfidence (CLARK's -c 0.5 -g 0)
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
+  uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
 };
 
 class Classifier {
@@ -134,11 +135,13 @@ class Classifier {
 };
 
 // file.cc:205-268: merged FASTA text of two FASTQ mates ("seq1" + 'N' + "seq2").
-std::string merge_paired(const std::string& file1, const std::string& file2);
+// min_quality_byte != 0: each mate's sequence is masked from its own quality line on the way (mic_qmask.h).
+std::string merge_paired(const std::string& file1, const std::string& file2, uint32_t min_quality_byte = 0);
 // The same text from the loaders' parallel merger (PairedFileFeeder: line counts, then batches of `batch_bytes` merged
 // independently); false when the files are not what it can cut (the caller then runs merge_paired, which ends the way
 // the reference ends on such files).
-bool merge_paired_parallel(const std::string& file1, const std::string& file2, unsigned threads, size_t batch_bytes, std::string& out);
+bool merge_paired_parallel(const std::string& file1, const std::string& file2, unsigned threads, size_t batch_bytes, std::string& out,
+                           uint32_t min_quality_byte = 0);
 // test hook: FASTQ text with the '+' and quality lines dropped, as the loaders hand it to the device (cuCLARK --strip-fastq)
 std::string strip_fastq_text(const std::string& in, size_t piece, bool scalar, int reps = 1);
 double strip_fastq_loaders_rate(const std::string& path, size_t chunk, unsigned threads, bool use_mmap);

@@ -96,6 +96,15 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
   };
   // ---- index (CuCLARK_hh.hh:1339-1534)
   if (nb == 0 || (map[0] != '>' && map[0] != '@')) { std::cerr << "Failed to recognize the format of the file." << std::endl; exit(-1); }
+  // --min-base-quality: what is classified on the host is masked on the host, by the same rule (mic_qmask.h) - a copy of the FASTQ
+  // text with 'N' for every masked base; merged pairs arrive masked (they are FASTA text)
+  std::vector<uint8_t> masked;
+  if (opt_.min_quality_byte && map[0] == '@') {
+    masked.resize(nb);
+    if (mic_fastq_mask_quality(map, nb, opt_.min_quality_byte, masked.data()) != MIC_OK)
+      die("--min-base-quality needs FASTQ records of four lines each (the input's line count is no multiple of four).");
+    map = masked.data();
+  }
   size_t cap = std::max<size_t>(1024, nb / 96);
   // index arrays live across segments: resizing a fresh vector zero-fills ~200 MB per 512 MB segment
   std::vector<uint64_t>&name_s = ix_[0], &name_e = ix_[1], &seq_s = ix_[2], &seq_e = ix_[3], &length = ix_[4];

@@ -3,6 +3,7 @@
 #ifndef MIC_CLASSIFIER_FEEDERS_HPP
 #define MIC_CLASSIFIER_FEEDERS_HPP
 #include "classifier_internal.hpp"
+#include "mic_qmask.h"
 
 #include <condition_variable>
 #include <deque>
@@ -377,9 +378,10 @@ class GzLines {
 };
 
 // paired-end FASTQ -> segments of the merged FASTA text ">id\nseq1Nseq2\n" (file.cc:205-268)
+// qmask != 0 (--min-base-quality): each mate's sequence is masked from its own quality line before it is written (mic_qmask.h)
 class PairedSource : public Classifier::SegmentSource {
  public:
-  PairedSource(const std::string& f1, const std::string& f2, size_t seg) : a_(f1), b_(f2), seg_(seg) {}
+  PairedSource(const std::string& f1, const std::string& f2, size_t seg, uint32_t qmask = 0) : a_(f1), b_(f2), seg_(seg), qmask_(qmask) {}
   bool ok() const { return a_.ok() && b_.ok(); }
   bool next(Classifier::Segment& s) override {
     if (done_) return false;
@@ -399,6 +401,15 @@ class PairedSource : public Classifier::SegmentSource {
       if (e1.empty() || e2.empty() || e1[0] != e2[0]) die("Error: read id does not match between files!");
       out += ">"; out += e1[0]; out += "\n";
       if (!(a_.line(l1) && b_.line(l2))) die("Error: Found read without sequence");
+      if (qmask_) {
+        // the '+' lines, then the quality lines (a record cut short has none: every base of it is masked)
+        std::string q1, q2, plus;
+        if (a_.line(plus) && b_.line(plus)) { a_.line(q1); b_.line(q2); }
+        mic_qmask_line((uint8_t*)&l1[0], l1.size(), (const uint8_t*)q1.data(), q1.size(), qmask_);
+        mic_qmask_line((uint8_t*)&l2[0], l2.size(), (const uint8_t*)q2.data(), q2.size(), qmask_);
+        out += l1; out += "N"; out += l2; out += "\n";
+        continue;
+      }
       out += l1; out += "N"; out += l2; out += "\n";   // NBN = 1 separator (parameters.hh:41)
       if (a_.line(l1) && b_.line(l2)) { a_.line(l1); b_.line(l2); }
     }
@@ -407,7 +418,7 @@ class PairedSource : public Classifier::SegmentSource {
     return true;
   }
  private:
-  GzLines a_, b_; size_t seg_; bool done_ = false, first_ = true;
+  GzLines a_, b_; size_t seg_; uint32_t qmask_; bool done_ = false, first_ = true;
 };
 
 class OneBuffer : public Classifier::SegmentSource {
@@ -577,16 +588,21 @@ class PairedFileFeeder : public Classifier::Feeder {
     bool room(size_t n) const { return w + n <= cap; }
     void put(const void* p, size_t n) { memcpy(d + w, p, n); w += n; }
     void put(char c) { d[w++] = (uint8_t)c; }
+    size_t pos() const { return w; }
+    uint8_t* at(size_t o) { return d + o; }
   };
   struct StringSink {
     std::string& s;
     bool room(size_t) const { return true; }
     void put(const void* p, size_t n) { s.append((const char*)p, n); }
     void put(char c) { s.push_back(c); }
+    size_t pos() const { return s.size(); }
+    uint8_t* at(size_t o) { return (uint8_t*)&s[o]; }
   };
 
  public:
-  PairedFileFeeder(const std::string& f1, const std::string& f2, unsigned threads) : threads_(std::max(1u, threads)) {
+  // qmask != 0 (--min-base-quality): the merged text carries 'N' for every base its mate's quality line masks (mic_qmask.h)
+  PairedFileFeeder(const std::string& f1, const std::string& f2, unsigned threads, uint32_t qmask = 0) : threads_(std::max(1u, threads)), qmask_(qmask) {
     const std::string* names[2] = {&f1, &f2};
     for (int i = 0; i < 2; ++i) {
       f_[i].fd = open(names[i]->c_str(), O_RDONLY);
@@ -669,11 +685,17 @@ class PairedFileFeeder : public Classifier::Feeder {
       s.put('>'); s.put(ia, la); s.put('\n');
       if (!A.next(p, n)) give_up();
       if (!s.room(n + 1)) return false;
+      const size_t at1 = s.pos(), n1 = n;
       s.put(p, n); s.put('N');
       if (!B.next(q, m)) give_up();
       if (!s.room(m + 1)) return false;
+      const size_t at2 = s.pos(), n2 = m;
       s.put(q, m); s.put('\n');
       if (!A.next(p, n) || !A.next(p, n) || !B.next(q, m) || !B.next(q, m)) give_up();
+      if (qmask_) {   // (p, n) and (q, m) are the mates' quality lines now: the sequences just written are masked in place
+        mic_qmask_line(s.at(at1), n1, p, n, qmask_);
+        mic_qmask_line(s.at(at2), n2, q, m, qmask_);
+      }
     }
   }
 
@@ -748,6 +770,7 @@ class PairedFileFeeder : public Classifier::Feeder {
 
   File f_[2];
   unsigned threads_;
+  uint32_t qmask_ = 0;
   bool ok_ = false, counted_ = false;
   std::atomic<bool> gave_up_{false};
   uint64_t pos_[2] = {0, 0}, records_ = 0, next_ = 0;

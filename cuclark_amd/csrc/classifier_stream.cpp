@@ -30,6 +30,9 @@ void Classifier::ingest_geometry(size_t total_bytes, size_t& bytes, size_t& work
   if (const char* env = getenv("MIC_INGEST_MB")) { long v = atol(env); if (v >= 1 && v <= 128) bytes = (size_t)v << 20; }
   if (const char* env = getenv("MIC_INGEST_KB")) { long v = atol(env); if (v >= 4) bytes = (size_t)v << 10; }
   if (const char* env = getenv("MIC_INGEST_WORKERS")) { long v = atol(env); if (v >= 1 && v <= 64) workers = (size_t)v; }
+  // --min-base-quality: FASTQ travels with its quality lines (the device masks from them), twice the bytes per read: slots of twice
+  // the size hold the batches they held before (128 MiB is mic_ingest_alloc's limit)
+  if (opt_.min_quality_byte) bytes = std::min<size_t>(bytes * 2, (size_t)128 << 20);
   // small inputs: do not pin more than the input needs
   while (bytes > (1u << 20) && total_bytes / workers < bytes / 2) bytes /= 2;
   if (total_bytes < bytes) workers = 1;
@@ -256,7 +259,8 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   size_t NL = T > ND + NW ? T - ND - NW : 1;
   if (S == 1) { ND = NW = NL = 1; }
   if (summary && S > 1) NL += NW;     // (no writer: its share of the threads loads)
-  const bool strip_ok = getenv("MIC_KEEP_QUALITY") == nullptr;
+  // (--min-base-quality: whole four-line records are uploaded, the packer reads the quality lines)
+  const bool strip_ok = getenv("MIC_KEEP_QUALITY") == nullptr && opt_.min_quality_byte == 0;
   const bool timing = getenv("MIC_CLI_TIMING") != nullptr;
 
   struct Item {

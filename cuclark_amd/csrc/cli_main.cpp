@@ -59,6 +59,9 @@ static void print_usage(const char* prog) {
                "                     (label<TAB>name_1<TAB>...<TAB>name_L per target) or from <DB>/../taxonomy; works without -R like --abundance\n";
   std::cout << "--min-confidence <c>, --min-gamma <g>, --highconfidence (= --min-confidence 0.75 --min-gamma 0.03), --min-abundance <a>:\n"
                "                     the filters of the abundance profile (CLARK's -c, -g, --highconfidence, -a; defaults 0.5, 0, 0)\n";
+  std::cout << "--min-base-quality <Q> [--quality-offset 33|64],  FASTQ: bases of Phred quality below Q (integer in [1,93]; quality characters\n"
+               "                     at offset 33, or 64) are treated as N: they belong to no k-mer.  Length, names and gamma's denominator\n"
+               "                     do not change; FASTA input has no qualities and is unaffected\n";
   std::cout << "--tsk, --extended, --light, --htsize <n>, --help, --version\n\n";
 }
 
@@ -74,18 +77,20 @@ int main(int argc, char** argv) {
       return 0;
     }
   }
-  // cuCLARK --merge-pairs <file1> <file2> <out.fa> [serial|parallel [threads [batch_bytes]]]: the paired-end merge alone
-  // (file.cc:205-268: the reference writes <file1>_ConcatenatedByCLARK.fa and classifies that), no device involved.
-  // "parallel" prints "gave up" and exits 3 when the loaders' merger hands the files to the serial reader.
+  // cuCLARK --merge-pairs <file1> <file2> <out.fa> [serial|parallel [threads [batch_bytes [threshold_byte]]]]: the paired-end merge
+  // alone (file.cc:205-268: the reference writes <file1>_ConcatenatedByCLARK.fa and classifies that), no device involved.
+  // "parallel" prints "gave up" and exits 3 when the loaders' merger hands the files to the serial reader.  threshold_byte: the
+  // merge as --min-base-quality runs it on the host (offset + Q, mic_qmask.h).
   if (argc >= 5 && std::string(argv[1]) == "--merge-pairs") {
     try {
       std::string text;
       const bool par = argc > 5 && std::string(argv[5]) == "parallel";
+      const uint32_t qm = argc > 8 ? (uint32_t)atoi(argv[8]) & 255u : 0u;
       if (par) {
         const unsigned th = argc > 6 ? (unsigned)atoi(argv[6]) : 4u;
         const size_t bb = argc > 7 ? (size_t)strtoull(argv[7], nullptr, 10) : (size_t)1 << 20;
-        if (!mic::merge_paired_parallel(argv[2], argv[3], th ? th : 1u, bb ? bb : 1, text)) { std::cerr << "gave up" << std::endl; return 3; }
-      } else text = mic::merge_paired(argv[2], argv[3]);
+        if (!mic::merge_paired_parallel(argv[2], argv[3], th ? th : 1u, bb ? bb : 1, text, qm)) { std::cerr << "gave up" << std::endl; return 3; }
+      } else text = mic::merge_paired(argv[2], argv[3], qm);
       FILE* f = fopen(argv[4], "wb");
       if (!f || fwrite(text.data(), 1, text.size(), f) != text.size() || fclose(f) != 0) { std::cerr << "Failed to write " << argv[4] << std::endl; return 1; }
       return 0;
@@ -150,6 +155,14 @@ int main(int argc, char** argv) {
   std::string abundance, rank_report, lineage;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
+  long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
+  // a whole decimal integer, nothing before or behind it
+  auto parse_int = [](const char* s, long& v) {
+    if (!*s || strlen(s) > 9) return false;
+    for (const char* c = s; *c; ++c) if (*c < '0' || *c > '9') return false;
+    v = atol(s);
+    return true;
+  };
 
   for (int i = 1; i < argc; i++) {
     std::string val(argv[i]);
@@ -202,6 +215,16 @@ int main(int argc, char** argv) {
         std::cerr << "The value of " << val << " should be a decimal number in [0," << (a ? 100 : 1) << "] with at most 9 decimals: " << argv[i] << std::endl;
         exit(1);
       }
+      continue;
+    }
+    if (val == "--min-base-quality") {
+      need("Please specify the minimum base quality!");
+      if (!parse_int(argv[i], min_q) || min_q < 1 || min_q > 93) { std::cerr << "The minimum base quality should be an integer in [1,93]: " << argv[i] << std::endl; exit(1); }
+      continue;
+    }
+    if (val == "--quality-offset") {
+      need("Please specify the quality offset!");
+      if (!parse_int(argv[i], q_offset) || (q_offset != 33 && q_offset != 64)) { std::cerr << "The quality offset should be 33 or 64: " << argv[i] << std::endl; exit(1); }
       continue;
     }
     if (val == "--highconfidence") { ab_filter.conf_num = 75; ab_filter.conf_den = 100; ab_filter.gamma_num = 3; ab_filter.gamma_den = 100; continue; }
@@ -275,6 +298,7 @@ int main(int argc, char** argv) {
   } else {
     gap = 0;
   }
+  if (q_offset && !min_q) { std::cerr << "--quality-offset goes with --min-base-quality <Q>." << std::endl; exit(1); }
   if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
   if ((!abundance.empty() || !rank_report.empty()) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
@@ -299,6 +323,7 @@ int main(int argc, char** argv) {
   o.abundance = abundance;
   o.abund_filter = ab_filter;
   o.rank_report = rank_report; o.lineage = lineage;
+  o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   mic::Classifier* classifier = nullptr;
   try {
     classifier = new mic::Classifier(o);

@@ -478,6 +478,30 @@ int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t*
 }
 }  // extern "C"
 
+// ---- base-quality mask: the rule of mic_qmask.h on the CPU (batches the host path classifies, the host merge of paired files) ------
+#include "mic_qmask.h"
+
+extern "C" int mic_fastq_mask_quality(const uint8_t* in, size_t nb, uint32_t threshold_byte, uint8_t* out) {
+  if (!in || !out || nb == 0 || in[0] != '@' || threshold_byte > 255) return MIC_E_INVALID;
+  size_t n_lines = 0;
+  for (const uint8_t* p = in; p < in + nb;) {
+    const uint8_t* nl = (const uint8_t*)memchr(p, '\n', (size_t)(in + nb - p));
+    ++n_lines;                                   // (an unterminated last line counts)
+    p = nl ? nl + 1 : in + nb;
+  }
+  if (n_lines % 4) return MIC_E_INVALID;
+  if (out != in) memmove(out, in, nb);
+  if (threshold_byte == 0) return MIC_OK;
+  // line ends are never rewritten, so the copy is walked: [s0, e0) the sequence line, [s1, e1) the quality line of each record
+  auto line_end = [&](size_t a) { const void* q = a < nb ? memchr(out + a, '\n', nb - a) : nullptr; return q ? (size_t)((const uint8_t*)q - out) : nb; };
+  for (size_t pos = 0; pos < nb;) {
+    const size_t s0 = line_end(pos) + 1, e0 = line_end(s0), s1 = line_end(e0 + 1) + 1, e1 = line_end(s1);
+    mic_qmask_line(out + s0, e0 - s0, out + s1, e1 - s1, threshold_byte);
+    pos = e1 + 1;
+  }
+  return MIC_OK;
+}
+
 // ---- rank roll-up: the rule of mic_rollup.h on the CPU (batches the host path classifies, estimate_abundance's cross-check) --------
 #include "mic_rollup.h"
 

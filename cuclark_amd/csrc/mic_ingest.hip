@@ -14,6 +14,7 @@
 #include "mi_clark.h"
 #include "mic_internal.h"
 #include "mic_fmt.h"
+#include "mic_qmask.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -37,6 +38,7 @@ int mic_bind_thread_near_device(int device, int on);
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
 MicAbund* mic_engine_abund(mic_engine* e);
 MicRollup* mic_engine_rollup(mic_engine* e);
+uint32_t* mic_engine_min_quality(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
 bool mic_peer_enable(int from, int to);
 
@@ -188,6 +190,7 @@ __global__ void __launch_bounds__(256) record_kernel(const uint8_t* __restrict__
   a.seq_s[r] = ss; a.seq_e[r] = ss + nbytes; a.length[r] = len;
   // containers reserved for the read: every part of L >= k nt takes 1 + ceil(L/8) <= 2 + L/8, parts are separated by at
   // least one byte; + slack for a trailing run that is dropped after its first containers were written, + the terminator
+  // (a base masked by its quality, pack_kernel<true>, is still one byte between two parts: the bound holds as it stands)
   a.bound[r] = (len < (uint32_t)k || status) ? 0u : nbytes / 8 + 2 * (nbytes / (uint32_t)(k + 1) + 1) + 8;
   if (status) atomicOr(&hdr[H_STATUS], status);
   (void)nb;
@@ -198,9 +201,16 @@ __global__ void __launch_bounds__(256) record_kernel(const uint8_t* __restrict__
 // are dropped.  Stored per part: one length slot + ceil(len/8) containers, 8 nt per u16, first nt in the top bits,
 // A=3 C=2 G=1 T/U=0, the last container left-aligned.  Reads are laid out at the reserved offsets rp[r] and end with a 0
 // length slot when they do not fill their reservation (the query kernel stops there, include/mi_clark.h).
+// QUAL (four-line FASTQ with a threshold set, mic_ingest_set_min_quality): the lane that loads raw[p] also loads the quality byte at
+// the same offset of the record's quality line and takes a masked base (mic_qmask.h) for an "other byte" - what an 'N' is.  The
+// quality line comes from the slot's LINE INDEX, passed in (no new per-record arrays): line 4r + 3, which ends at
+// line_start[4r + 4] - 1 - the virtual line end of an unterminated last line included (lines_finish_kernel).  Both loads are byte
+// loads at consecutive addresses across the wavefront.  <false> is the kernel as it was; every launch without a threshold takes it.
+template <bool QUAL>
 __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ raw, const uint32_t* __restrict__ seq_s,
                                                    const uint32_t* __restrict__ seq_e, const uint32_t* __restrict__ rp,
-                                                   uint16_t* __restrict__ cont, uint32_t n_reads, int k) {
+                                                   uint16_t* __restrict__ cont, uint32_t n_reads, int k,
+                                                   const uint32_t* __restrict__ line_start, uint32_t c0) {
   __shared__ uint8_t s_codes[4][80];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -211,6 +221,8 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ r
     if (o1 == o0) continue;                       // shorter than k: nothing stored (CuCLARK_hh.hh:1633)
     uint16_t* out = cont + o0;
     const uint32_t s = seq_s[r], e = seq_e[r];
+    uint32_t qs = 0, qn = 0;                      // QUAL: where the record's quality line starts, its bytes
+    if (QUAL) { qs = line_start[4 * r + 3]; qn = line_start[4 * r + 4] - 1u - qs; }
     uint32_t hdr = 0, run = 0;                    // header slot of the open part (relative), its nucleotides so far
     auto close_run = [&]() {
       if (run >= (uint32_t)k) {
@@ -232,6 +244,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ r
         const uint32_t b = raw[p], u = b & 0xDFu;
         if (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U') { cls = 0; code = (0x4Bu >> (2 * ((u >> 1) & 3u))) & 3u; }
         else cls = b == '\n' ? 1 : 2;
+        if (QUAL && mic_qmask_masked(raw + qs, qn, p - s, c0)) cls = 2;
       }
       const uint64_t m_nt = __ballot(cls == 0), m_ot = __ballot(cls == 2);
       int lo = 0;
@@ -465,8 +478,11 @@ __global__ void text_facts_kernel(const uint8_t* __restrict__ raw, uint32_t nb, 
 }
 
 // one wavefront per record: ">id\n" seq1 "N" seq2 "\n" at off[r] - off[r0]
+// QUAL (a threshold byte c0 is set on the engine): each mate's sequence is copied with 'N' in place of every base its own quality
+// line (line 4r + 3 of its text) masks (mic_qmask.h); the lengths are those of pair_len_kernel either way
+template <bool QUAL>
 __global__ void __launch_bounds__(256) pair_merge_kernel(PairText A, PairText B, uint64_t r0, uint64_t r1, const unsigned long long* __restrict__ off,
-                                                         uint8_t* __restrict__ dst) {
+                                                         uint8_t* __restrict__ dst, uint32_t c0) {
   const int lane = threadIdx.x & 63;
   const uint64_t r = r0 + (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= r1) return;
@@ -479,13 +495,23 @@ __global__ void __launch_bounds__(256) pair_merge_kernel(PairText A, PairText B,
   for (uint32_t i = lane; i < la; i += 64) o[1 + i] = p[ia + i];
   if (lane == 0) o[1 + la] = '\n';
   o += la + 2;
+  const uint8_t* u = nullptr; uint32_t un = 0;       // QUAL: the mate's quality line
   pair_line(A, 4 * r + 1, p, n);
-  for (uint32_t i = lane; i < n; i += 64) o[i] = p[i];
+  if (QUAL) pair_line(A, 4 * r + 3, u, un);
+  for (uint32_t i = lane; i < n; i += 64) o[i] = (QUAL && mic_qmask_masked(u, un, i, c0)) ? (uint8_t)'N' : p[i];
   if (lane == 0) o[n] = 'N';
   o += n + 1;
   pair_line(B, 4 * r + 1, q, m);
-  for (uint32_t i = lane; i < m; i += 64) o[i] = q[i];
+  if (QUAL) pair_line(B, 4 * r + 3, u, un);
+  for (uint32_t i = lane; i < m; i += 64) o[i] = (QUAL && mic_qmask_masked(u, un, i, c0)) ? (uint8_t)'N' : q[i];
   if (lane == 0) o[m] = '\n';
+}
+
+void launch_pair_merge(const PairText& A, const PairText& B, uint64_t r0, uint64_t r1, const unsigned long long* off, uint8_t* dst, uint32_t c0,
+                       hipStream_t st) {
+  const unsigned blocks = (unsigned)((r1 - r0 + 3) / 4);
+  if (c0) pair_merge_kernel<true><<<blocks, 256, 0, st>>>(A, B, r0, r1, off, dst, c0);
+  else pair_merge_kernel<false><<<blocks, 256, 0, st>>>(A, B, r0, r1, off, dst, 0u);
 }
 
 struct Slot {
@@ -1038,6 +1064,9 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   const bool no_csv = (flags & MIC_INGEST_NO_CSV) != 0;
   const uint32_t lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;      // lines per FASTQ record
   if (!e || !out) return mic_set_error(MIC_E_INVALID, "null argument");
+  // the base-quality threshold of the slot's engine (0: none): four-line FASTQ is then packed by pack_kernel<true>
+  const uint32_t c0 = *mic_engine_min_quality(e);
+  if (c0 && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while a base-quality threshold is set: the quality lines are gone");
   Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
   if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
   if (n_bytes == 0 || n_bytes > g->max_bytes) return mic_set_error(MIC_E_INVALID, "batch of %zu bytes does not fit the slot (%zu)", n_bytes, g->max_bytes);
@@ -1100,7 +1129,8 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   {
     unsigned blocks = (n_reads + 3) / 4, cap = (unsigned)ncu * 64u;
     if (blocks > cap) blocks = cap;
-    pack_kernel<<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k);
+    if (c0 && !fasta) pack_kernel<true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0);
+    else pack_kernel<false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u);
   }
   // rank roll-up started on the slot's engine: the rows instantiation of the same kernel fills the slot's row buffer.  One engine:
   // rows of the --extended width, so that a batch is handed back exactly when it is handed back without roll-up (a row that does
@@ -1178,6 +1208,13 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+lengths %.0f us, csv %.0f us\n", slot_id, nb, n_reads,
             (t1 - t0) * 1e6, (t2 - t1) * 1e6, (t3 - t2) * 1e6);
   }
+  return MIC_OK;
+}
+
+int mic_ingest_set_min_quality(mic_engine* e, uint32_t threshold_byte) {
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  if (threshold_byte > 255) return mic_set_error(MIC_E_INVALID, "a threshold byte is 0 (off) .. 255, got %u", threshold_byte);
+  *mic_engine_min_quality(e) = threshold_byte;
   return MIC_OK;
 }
 
@@ -1332,7 +1369,7 @@ int mic_pairs_merge_to_slot(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r
     return mic_set_error(MIC_E_UNSUPPORTED, "device %d has no peer access to device %d, where the inflated text lives", g->device, p->device);
   ITRY(hipSetDevice(g->device));
   Slot& s = g->slots[slot_id];
-  pair_merge_kernel<<<(unsigned)((r1 - r0 + 3) / 4), 256, 0, s.stream>>>(p->t[0], p->t[1], r0, r1, p->d_off, s.d_raw);
+  launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, s.d_raw, *mic_engine_min_quality(e), s.stream);
   ITRY(hipGetLastError());
   *n_bytes = (size_t)(o1 - o0);
   return MIC_OK;
@@ -1348,7 +1385,7 @@ int mic_pairs_text(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r1, void* 
   ITRY(hipSetDevice(p->device));
   uint8_t* d = nullptr;
   ITRY(hipMalloc(&d, *n_bytes + 16));
-  pair_merge_kernel<<<(unsigned)((r1 - r0 + 3) / 4), 256, 0, 0>>>(p->t[0], p->t[1], r0, r1, p->d_off, d);
+  launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, d, *mic_engine_min_quality(e), 0);
   hipError_t he = hipGetLastError();
   if (he == hipSuccess) he = hipMemcpy(host_dst, d, *n_bytes, hipMemcpyDeviceToHost);
   hipFree(d);

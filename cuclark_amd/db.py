@@ -310,13 +310,18 @@ class MiClarkDB:
         self._ingest = dict(raw=[_as_np(raw[i], (max_bytes,), np.uint8) for i in range(n_slots)], max_bytes=max_bytes)
         return self._ingest["raw"]
 
-    def ingest_classify(self, slot, data, paired=False, csv=True):
+    def ingest_set_min_quality(self, q, offset=33):
+        """Base-quality mask of this engine's ingest (mic_ingest_set_min_quality): bases of four-line FASTQ whose Phred quality is
+        below q (quality characters at `offset`, 33 or 64) take no part in any k-mer; q = 0 clears it."""
+        check(self.L.mic_ingest_set_min_quality(self.h, (int(offset) + int(q)) if q else 0))
+
+    def ingest_classify(self, slot, data, paired=False, csv=True, flags=0):
         """data: bytes of whole records.  Returns dict(status, n_reads, csv (bytes), results (u32[n,8] or None)).
-        csv=False: MIC_INGEST_NO_CSV (no CSV text, csv is b"")."""
+        csv=False: MIC_INGEST_NO_CSV (no CSV text, csv is b""); flags: further MIC_INGEST_* flags."""
         buf = np.frombuffer(data, np.uint8)
         self._ingest["raw"][slot][: buf.size] = buf
         out = _lib.MicIngestResult()
-        flags = int(bool(paired)) | (0 if csv else _lib.MIC_INGEST_NO_CSV)
+        flags = int(flags) | int(bool(paired)) | (0 if csv else _lib.MIC_INGEST_NO_CSV)
         check(self.L.mic_ingest_classify(self.h, slot, buf.size, flags, C.byref(out)))
         r = dict(status=int(out.status), n_reads=int(out.n_reads), n_lines=int(out.n_lines), csv=None, results=None)
         if out.status == 0:

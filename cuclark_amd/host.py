@@ -99,6 +99,19 @@ def parse_threshold(text, max_int=1):
     return int(num.value), int(den.value)
 
 
+def mask_quality(data, q, offset=33, threshold_byte=None):
+    """mic_fastq_mask_quality: the bytes of four-line FASTQ text with every base whose Phred quality is below q (quality characters
+    at `offset`) replaced by 'N' - csrc/mic_qmask.h's rule on the CPU; q = 0: a plain copy.  threshold_byte overrides offset + q.
+    ValueError when the text does not start with '@' or its line count is no multiple of four."""
+    src = np.frombuffer(bytes(data), np.uint8)
+    out = np.empty(max(src.size, 1), np.uint8)
+    c0 = int(threshold_byte) if threshold_byte is not None else ((int(offset) + int(q)) if q else 0)
+    rc = _lib.load().mic_fastq_mask_quality(src.ctypes.data if src.size else None, src.size, c0, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_fastq_mask_quality: not four-line FASTQ text, or a threshold byte above 255 ({rc})")
+    return out[: src.size].tobytes()
+
+
 def abund_filter(confidence="0.5", gamma="0"):
     """mic_abund_filter from decimal strings (CLARK's defaults: -c 0.5 -g 0)."""
     cn, cd = parse_threshold(confidence)

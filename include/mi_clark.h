@@ -337,6 +337,25 @@ int mic_ingest_fetch_group_rows(mic_engine* owner, size_t slot, size_t part, uin
 #define MIC_GROUP_STATS_FIELDS 10
 int mic_ingest_group_stats(mic_engine* owner, double* out, size_t cap);
 int mic_ingest_free(mic_engine* e);
+/* ---- base-quality mask: FASTQ bases below a Phred threshold take no part in any k-mer (csrc/mic_qmask.h: the rule) ---------
+ * The reference reads no qualities (CuCLARK_hh.hh:1496-1523 steps over the quality line).  With a threshold byte c0 = offset + Q
+ * (offset 33 or 64), byte i of a record's sequence line is MASKED iff the record's quality line has no byte i or that byte is below
+ * c0 (unsigned compare; lines are taken without their '\n', a '\r' belongs to the line; surplus quality characters are ignored).
+ * A masked byte is to the packer what an 'N' is: it ends the ACGTU run and belongs to no k-mer.  Length column, names, the
+ * separator of a merged pair and gamma's denominator do not change: the result is that of the same text with every masked base
+ * replaced by 'N', byte for byte.
+ * mic_ingest_set_min_quality  engine state; 0 clears it, a value above 255 is MIC_E_INVALID.  From then on it applies to every
+ *                             mic_ingest_classify / mic_ingest_classify_group call owned by this engine whose text is four-line
+ *                             FASTQ (uploaded or MIC_INGEST_RESIDENT_FASTQ: masked in the packer), and to mic_pairs_merge_to_slot /
+ *                             mic_pairs_text on this engine (each mate masked from its own quality line while it is merged).
+ *                             MIC_INGEST_FASTQ_2LINE while a threshold is set: MIC_E_INVALID (the qualities are gone).  FASTA text
+ *                             is unaffected.
+ * mic_fastq_mask_quality      the rule on the CPU, no device needed: a copy of four-line FASTQ text with the masked bases replaced
+ *                             by 'N' (in == out is allowed; threshold_byte 0: a plain copy).  MIC_E_INVALID when the text does not
+ *                             start with '@' or its line count (an unterminated last line counts) is no multiple of four; nothing
+ *                             is written then.  For what stays on the host: batches handed back (MIC_INGEST_FALLBACK), the batch path. */
+int mic_ingest_set_min_quality(mic_engine* e, uint32_t threshold_byte);
+int mic_fastq_mask_quality(const uint8_t* in, size_t nb, uint32_t threshold_byte, uint8_t* out);
 /* ---- compressed input: one gzip member inflated on the device ------------------------------------------------
  * Replaces the `gunzip` the reference's scripts run in front of the classifier (classify_metagenome.sh:116-142) for the
  * common cases: ONE member without a preset dictionary (what `gzip` writes), or a whole block-gzip file (BGZF: members with a
