@@ -19,6 +19,7 @@ MIC_FLAG_DENSE_PATH = 2
 MIC_ROW_INVALID = 0xFFFFFFFF
 MIC_ROLLUP_WORDS, MIC_ROLLUP_MAX_LEVELS = 8, 7
 MIC_ROLLUP_UNRESOLVED, MIC_ROLLUP_PENDING = 0xFFFFFFFF, 0xFFFFFFFE
+MIC_DENSITY_WORDS, MIC_DENSITY_CONF_BINS, MIC_DENSITY_GAMMA_BINS = 5153, 51, 101
 MIC_LAYOUT_AUTO, MIC_LAYOUT_DIRECT, MIC_LAYOUT_MINIMIZER, MIC_LAYOUT_SUPER, MIC_LAYOUT_SUPER2 = 0, 1, 2, 3, 4
 
 
@@ -152,6 +153,12 @@ SYMBOLS = [
     ("mic_rollup_fetch", C.c_int, [_VP, _VP, _SZ]),
     ("mic_rollup_stop", C.c_int, [_VP]),
     ("mic_ingest_rollup_rows", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("mic_density_start", C.c_int, [_VP]),
+    ("mic_density_fetch", C.c_int, [_VP, _VP, _SZ]),
+    ("mic_density_stop", C.c_int, [_VP]),
+    ("mic_density_device", C.c_int, [_VP, _VP, _VP, _SZ, _VP, _VP]),
+    ("mic_density_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, _VP]),
+    ("mic_density_format", C.c_long, [_VP, _SZ, C.c_int, C.c_char_p, _SZ]),
     ("mic_format_ratio_g", C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p]),
     ("mic_key_bytes_rule", C.c_int, [C.c_uint64, C.c_int]),
     ("mic_index_reads", C.c_long, [_VP, _SZ, _SZ, _U64P, _U64P, _U64P, _U64P, _U64P]),

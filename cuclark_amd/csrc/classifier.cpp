@@ -257,6 +257,11 @@ void Classifier::reset_counts() {
     std::lock_guard<std::mutex> lk(count_mu_);
     host_rollup_.assign(lineage_.n_counters(), 0);
   }
+  if (densing()) {
+    for (mic_engine* e : engines_) check(mic_density_start(e), "density counters");
+    std::lock_guard<std::mutex> lk(count_mu_);
+    host_density_.assign(MIC_DENSITY_WORDS, 0);
+  }
   if (!counting()) return;
   for (mic_engine* e : engines_) check(mic_abundance_start(e, &opt_.abund_filter), "abundance counters");
   std::lock_guard<std::mutex> lk(count_mu_);
@@ -265,6 +270,14 @@ void Classifier::reset_counts() {
 
 // a batch the host path classified (results: MIC_RESULT_WORDS per read, norm: the Length column of each read)
 void Classifier::count_host(const std::vector<uint32_t>& results, const std::vector<uint32_t>& norm) {
+  if (densing()) {
+    std::vector<uint64_t> d(MIC_DENSITY_WORDS, 0);
+    check(mic_density_host(results.data(), norm.data(), norm.size(), (int)opt_.k, (uint32_t)names_.size(), d.data()), "density (host path)");
+    std::lock_guard<std::mutex> lk(count_mu_);
+    if (host_density_.size() != d.size()) host_density_.assign(d.size(), 0);
+    for (size_t i = 0; i < d.size(); ++i) host_density_[i] += d[i];
+  }
+  if (!counting()) return;
   std::vector<uint64_t> c(names_.size() + 2, 0);
   check(mic_abundance_host(results.data(), norm.data(), norm.size(), (int)opt_.k, (uint32_t)names_.size(), &opt_.abund_filter, c.data()),
         "abundance (host path)");
@@ -281,6 +294,17 @@ std::vector<uint64_t> Classifier::abundance_counts() {
   }
   std::lock_guard<std::mutex> lk(count_mu_);
   for (size_t i = 0; i < host_counts_.size() && i < total.size(); ++i) total[i] += host_counts_[i];
+  return total;
+}
+
+std::vector<uint64_t> Classifier::density_counts() {
+  std::vector<uint64_t> total(MIC_DENSITY_WORDS, 0), part(MIC_DENSITY_WORDS);
+  for (mic_engine* e : engines_) {
+    check(mic_density_fetch(e, part.data(), part.size()), "density counters");
+    for (size_t i = 0; i < part.size(); ++i) total[i] += part[i];
+  }
+  std::lock_guard<std::mutex> lk(count_mu_);
+  for (size_t i = 0; i < host_density_.size() && i < total.size(); ++i) total[i] += host_density_[i];
   return total;
 }
 
@@ -440,6 +464,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
+  if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");
   std::ifstream o_fd(objects), r_fd(results);
   std::string o_line, r_line;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;
@@ -520,6 +545,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
   if (!list_mode) { one(f1, f2, results, false); return; }
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
+  if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");
   std::ifstream o1(f1), o2(f2), r_fd(results);
   std::string a, b, r;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;

@@ -36,6 +36,7 @@ struct Options {
   std::string abundance;                                     // --abundance <file>: the abundance profile is counted (mic_abundance_*)
   mic_abund_filter abund_filter = {5, 10, 0, 1};             // --min-confidence / --min-gamma / --highconfidence (CLARK's -c 0.5 -g 0)
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
+  std::string density;                                       // --density <file>: the score densities are counted (mic_density_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
 };
 
@@ -91,6 +92,8 @@ class Classifier {
   // --rank-report: the roll-up counters of the run (include/mi_clark.h: [0] no hit, [1] unresolved, [2 + off_l + g]), summed the same
   // way, and the lineage they were counted along (from --lineage, else from <database directory>/../taxonomy)
   std::vector<uint64_t> rollup_counts();
+  // --density: the MIC_DENSITY_WORDS counters of the run (csrc/mic_density.h), summed the same way
+  std::vector<uint64_t> density_counts();
   const rank::Lineage& lineage() const { return lineage_; }
 
   std::string db_name() const;  // getdbName, CuCLARK_hh.hh:580-591
@@ -124,11 +127,12 @@ class Classifier {
   // --abundance: every run over the input starts the counters afresh (a run the feeder gives up is repeated from the start)
   bool counting() const { return !opt_.abundance.empty(); }
   bool ranking() const { return !opt_.rank_report.empty(); }
+  bool densing() const { return !opt_.density.empty(); }
   rank::Lineage lineage_;
   std::vector<uint64_t> host_rollup_;
   void reset_counts();
   void count_host(const std::vector<uint32_t>& results, const std::vector<uint32_t>& norm);
-  std::vector<uint64_t> host_counts_;
+  std::vector<uint64_t> host_counts_, host_density_;
   std::mutex count_mu_;
   bool csv_out_ = true;                       // the current run writes a result CSV (false: summary-only --abundance run)
   double prelude_s_ = 0;                      // seconds spent inflating a compressed input before the streaming path started

@@ -195,8 +195,8 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       std::vector<char> line(line_cap);
       std::vector<uint32_t> dense;
       std::vector<uint32_t> ab_res, ab_norm;        // --abundance: the batch's result rows as the CSV shows them, and the Length column
-      if (counting()) ab_res.resize(cnt * MIC_RESULT_WORDS);
-      if (counting() || ranking()) ab_norm.resize(cnt);
+      if (counting() || densing()) ab_res.resize(cnt * MIC_RESULT_WORDS);
+      if (counting() || ranking() || densing()) ab_norm.resize(cnt);
       // --rank-report: this batch's roll-up counters, from its sparse rows and - a read at a time - the dense counts of the rows that did not fit
       std::vector<uint64_t> ru_counts(ranking() ? lineage_.n_counters() : 0, 0);
       const uint32_t* res = L.results + lb * slot_reads_ * MIC_RESULT_WORDS;
@@ -233,8 +233,8 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
           }
           dn = dense.data();
         }
-        if (counting()) memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
-        if (counting() || ranking()) ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
+        if (counting() || densing()) memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
+        if (counting() || ranking() || densing()) ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
         if (ranking() && dn)
           check(mic_rollup_host(nullptr, 0, dn, &ab_norm[i], 1, k, T, lineage_.n_levels, lineage_.group_of.data(), &opt_.abund_filter, nullptr, nullptr,
                                 ru_counts.data()), "roll-up (host path, dense counts)");
@@ -244,7 +244,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
         if (w < 0) die("CSV line too long");
         s.append(line.data(), (size_t)w);
       }
-      if (counting()) count_host(ab_res, ab_norm);
+      if (counting() || densing()) count_host(ab_res, ab_norm);       // (--abundance and --density: each counts its own)
       if (ranking()) {
         check(mic_rollup_host(rows, row_words, nullptr, ab_norm.data(), cnt, k, T, lineage_.n_levels, lineage_.group_of.data(), &opt_.abund_filter,
                               nullptr, nullptr, ru_counts.data()), "roll-up (host path)");

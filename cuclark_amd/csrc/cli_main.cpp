@@ -17,6 +17,7 @@
 
 #include "abundance_table.hpp"
 #include "classifier.hpp"
+#include "density_report.hpp"
 #include "mic_abund.h"
 
 #define MAXK 32
@@ -57,6 +58,9 @@ static void print_usage(const char* prog) {
   std::cout << "--rank-report <file> [--lineage <tsv>],  also resolve every object at the lowest rank whose confidence passes --min-confidence\n"
                "                     and count the objects per rank and group into <file>; the lineage of the targets comes from <tsv>\n"
                "                     (label<TAB>name_1<TAB>...<TAB>name_L per target) or from <DB>/../taxonomy; works without -R like --abundance\n";
+  std::cout << "--density <file>,    also count the objects per confidence score and per gamma score (bins of 0.01, and the joint table) into <file>:\n"
+               "                     CLARK's evaluate_density reports, whose cumulative columns are what --min-confidence / --min-gamma keep;\n"
+               "                     works without -R like --abundance\n";
   std::cout << "--min-confidence <c>, --min-gamma <g>, --highconfidence (= --min-confidence 0.75 --min-gamma 0.03), --min-abundance <a>:\n"
                "                     the filters of the abundance profile (CLARK's -c, -g, --highconfidence, -a; defaults 0.5, 0, 0)\n";
   std::cout << "--min-base-quality <Q> [--quality-offset 33|64],  FASTQ: bases of Phred quality below Q (integer in [1,93]; quality characters\n"
@@ -152,7 +156,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage;
+  std::string abundance, rank_report, lineage, density;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -199,6 +203,7 @@ int main(int argc, char** argv) {
     }
     if (val == "--light") { light = true; continue; }
     if (val == "--abundance") { need("Please specify the file of the abundance profile!"); abundance = argv[i]; continue; }
+    if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
     if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
     if (val == "--lineage") {
       need("Please specify the lineage file!");
@@ -300,11 +305,11 @@ int main(int argc, char** argv) {
   }
   if (q_offset && !min_q) { std::cerr << "--quality-offset goes with --min-base-quality <Q>." << std::endl; exit(1); }
   if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
-  if ((!abundance.empty() || !rank_report.empty()) && i_results < 0 && ext) {
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty()) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty())) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty())) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -323,6 +328,7 @@ int main(int argc, char** argv) {
   o.abundance = abundance;
   o.abund_filter = ab_filter;
   o.rank_report = rank_report; o.lineage = lineage;
+  o.density = density;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   mic::Classifier* classifier = nullptr;
   try {
@@ -344,6 +350,14 @@ int main(int argc, char** argv) {
       if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
         throw std::runtime_error("Failed to write the rank report: " + rank_report);
       std::cout << " - Rank report stored in " << rank_report << std::endl;
+    }
+    if (!density.empty()) {
+      const std::vector<uint64_t> counts = classifier->density_counts();
+      const std::string report = mic::density::format_report(counts.data());
+      FILE* f = fopen(density.c_str(), "wb");
+      if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the density report: " + density);
+      std::cout << " - Density report stored in " << density << std::endl;
     }
   } catch (const std::exception& ex) {
     std::cerr << ex.what() << std::endl;

@@ -24,6 +24,7 @@
 #include "mic_abund.h"
 #include "mic_rollup.h"
 #include "rank_report.hpp"
+#include "result_csv.hpp"
 
 namespace {
 
@@ -33,53 +34,6 @@ namespace {
                " [-g <min gamma in [0,1]>] [-a <min abundance in [0,100]>] [--highconfidence]"
                " [--rank-report <file> [--lineage <tsv>]]" << std::endl;
   exit(1);
-}
-
-// value of the printed decimal text >= num / den?  ("%g" forms: "0.762887", "1", "5e-05", "-0"; anything else - "-nan" - is no
-// number and fails every positive threshold)
-bool decimal_at_least(const std::string& s, uint64_t num, uint64_t den) {
-  if (num == 0) return true;
-  size_t i = 0;
-  if (i < s.size() && (s[i] == '-' || s[i] == '+')) { if (s[i] == '-') return false; ++i; }     // (a negative value, or -0)
-  unsigned __int128 m = 0;
-  int exp10 = 0, digits = 0;
-  bool point = false;
-  for (; i < s.size(); ++i) {
-    const char c = s[i];
-    if (c == '.') { if (point) return false; point = true; continue; }
-    if (c < '0' || c > '9') break;
-    ++digits;
-    if (m < (unsigned __int128)1 << 100) { m = m * 10 + (unsigned)(c - '0'); if (point) --exp10; }
-    else if (!point) ++exp10;
-  }
-  if (digits == 0) return false;
-  if (i < s.size()) {
-    if (s[i] != 'e' && s[i] != 'E') return false;
-    ++i;
-    int sign = 1, e = 0;
-    if (i < s.size() && (s[i] == '-' || s[i] == '+')) { if (s[i] == '-') sign = -1; ++i; }
-    if (i >= s.size()) return false;
-    for (; i < s.size(); ++i) { if (s[i] < '0' || s[i] > '9') return false; if (e < 1000) e = e * 10 + (s[i] - '0'); }
-    exp10 += sign * e;
-  }
-  if (m == 0) return false;
-  // m 10^exp10 >= num / den  <=>  m den 10^exp10 >= num
-  unsigned __int128 lhs = m * den, rhs = num;
-  if (exp10 >= 0) { if (exp10 > 12) return true; for (int j = 0; j < exp10; ++j) lhs *= 10; }
-  else {
-    int sh = -exp10;
-    for (; sh > 0 && lhs % 10 == 0; --sh) lhs /= 10;       // (trailing zeros of a long mantissa first: rhs stays in range)
-    if (sh > 26) return false;
-    for (int j = 0; j < sh; ++j) rhs *= 10;
-  }
-  return lhs >= rhs;
-}
-
-bool parse_u32(const std::string& s, uint64_t& v) {
-  if (s.empty() || s.size() > 10) return false;
-  v = 0;
-  for (char c : s) { if (c < '0' || c > '9') return false; v = v * 10 + (uint64_t)(c - '0'); }
-  return v <= 0xFFFFFFFFull;
 }
 
 }  // namespace
@@ -174,27 +128,21 @@ int main(int argc, char** argv) {
       if (ranks && ru_labels.empty()) { std::cerr << "--rank-report needs the header line of an --extended result file; " << path << " has none." << std::endl; return 1; }
       // the last seven fields (the object name may hold commas)
       std::string fld[7];
-      size_t end = line.size();
-      bool ok = true;
-      for (int j = 6; j >= 0; --j) {
-        const size_t c = line.rfind(',', end == 0 ? std::string::npos : end - 1);
-        if (c == std::string::npos || end == 0) { ok = false; break; }
-        fld[j] = line.substr(c + 1, end - c - 1);
-        end = c;
-      }
+      size_t end = 0;
+      bool ok = mic::csv::last_seven(line, fld, &end);
       uint64_t s1 = 0, s2 = 0;
-      if (!ok || !parse_u32(fld[3], s1) || !parse_u32(fld[5], s2)) {
+      if (!ok || !mic::csv::parse_u32(fld[3], s1) || !mic::csv::parse_u32(fld[5], s2)) {
         std::cerr << "Failed to read line " << ln << " of " << path << ": not a result line of CLARK's format." << std::endl;
         return 1;
       }
       const std::string& first = fld[2];
-      const bool gamma = decimal_at_least(fld[1], f.gamma_num, f.gamma_den);
+      const bool gamma = mic::decimal::at_least(fld[1], f.gamma_num, f.gamma_den);
       if (ranks) {      // the T count columns in front of the last seven
         ru_tg.clear(); ru_cn.clear();
         for (size_t t = ru_labels.size(); t-- > 0 && ok;) {
           const size_t c = end == 0 ? std::string::npos : line.rfind(',', end - 1);
           uint64_t v = 0;
-          if (c == std::string::npos || !parse_u32(line.substr(c + 1, end - c - 1), v)) { ok = false; break; }
+          if (c == std::string::npos || !mic::csv::parse_u32(line.substr(c + 1, end - c - 1), v)) { ok = false; break; }
           if (v) { ru_tg.push_back((uint32_t)t); ru_cn.push_back((uint32_t)v); }
           end = c;
         }

@@ -172,6 +172,7 @@ struct mic_engine {
   uint32_t part = 0, n_parts = 0;   // mic_db_set_part: this engine answers for part `part` of `n_parts` of the database
   MicAbund abund;                   // mic_abundance_*: the engine's counters (mic_abund.hip)
   MicRollup rollup;                 // mic_rollup_*: the engine's lineage and counters (mic_rollup.hip)
+  MicDensity density;               // mic_density_*: the engine's counters (mic_density.hip)
 };
 
 namespace {
@@ -611,6 +612,7 @@ void** mic_engine_ingest_slot(mic_engine* e) { return &e->ingest; }
 MicAbund* mic_engine_abund(mic_engine* e) { return &e->abund; }
 uint32_t* mic_engine_min_quality(mic_engine* e) { return &e->min_quality; }
 MicRollup* mic_engine_rollup(mic_engine* e) { return &e->rollup; }
+MicDensity* mic_engine_density(mic_engine* e) { return &e->density; }
 uint32_t mic_engine_row_words(const mic_engine* e) { return e->cfg.row_words; }
 hipStream_t mic_engine_stream(mic_engine* e) { return e->stream; }
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down) { *up = e->up_stream; *down = e->down_stream; }
@@ -714,6 +716,7 @@ int mic_destroy(mic_engine* e) {
   if (e->d_crowd) hipFree(e->d_crowd);
   if (e->abund.d_counts) hipFree(e->abund.d_counts);
   if (e->rollup.d_counts) hipFree(e->rollup.d_counts);
+  if (e->density.d_counts) hipFree(e->density.d_counts);
   if (e->rollup.d_block) hipFree(e->rollup.d_block);
   if (e->ev0) mic_event_put(e->ev0);
   if (e->ev1) mic_event_put(e->ev1);

@@ -478,6 +478,28 @@ int mic_abund_parse(const char* text, uint32_t max_int, uint64_t* num, uint64_t*
 }
 }  // extern "C"
 
+// ---- score densities: the rule of mic_density.h on the CPU (batches the host path classifies), and the report as text --------------
+#include "density_report.hpp"
+
+extern "C" {
+int mic_density_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets, uint64_t* counts) {
+  if (!counts || (n_reads && !results)) return MIC_E_INVALID;
+  for (size_t r = 0; r < n_reads; ++r) {
+    const uint32_t cell = mic_density_cell(results + r * MIC_RESULT_WORDS, norm ? norm[r] : 0u, k, n_targets);
+    ++counts[cell == MIC_DENSITY_NONE ? 1 : 2 + cell];
+  }
+  counts[0] += n_reads;
+  return MIC_OK;
+}
+
+long mic_density_format(const uint64_t* counts, size_t n, int which, char* buf, size_t cap) {
+  if (!counts || n != MIC_DENSITY_WORDS || which < 0 || which > 2) return MIC_E_INVALID;
+  const std::string text = mic::density::format_report(counts, (mic::density::Which)which);
+  if (buf && text.size() < cap) memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
+}
+}  // extern "C"
+
 // ---- base-quality mask: the rule of mic_qmask.h on the CPU (batches the host path classifies, the host merge of paired files) ------
 #include "mic_qmask.h"
 

@@ -38,6 +38,7 @@ int mic_bind_thread_near_device(int device, int on);
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
 MicAbund* mic_engine_abund(mic_engine* e);
 MicRollup* mic_engine_rollup(mic_engine* e);
+MicDensity* mic_engine_density(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
 bool mic_peer_enable(int from, int to);
@@ -1172,6 +1173,11 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     ITRY(mic_launch_rollup(ru, s.d_ru_rows, s.ru_row_words, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ru.filter, s.d_rollup, nullptr,
                            ru.d_counts, s.d_hdr + H_STATUS, st));
     if (s.h_rollup) ITRY(hipMemcpyAsync(s.h_rollup, s.d_rollup, (size_t)n_reads * MIC_ROLLUP_WORDS * 4, hipMemcpyDeviceToHost, st));
+  }
+  {  // score densities (mic_density_start on the slot's engine, the owner of a table-sharded batch), under the same status word
+    MicDensity& dn = *mic_engine_density(e);
+    if (dn.on && dn.d_counts)
+      ITRY(mic_launch_density(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ncu, dn.d_counts, s.d_hdr + H_STATUS, st));
   }
   if (no_csv && g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, st));
   ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));

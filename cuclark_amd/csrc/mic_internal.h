@@ -229,6 +229,17 @@ struct MicAbund {
 hipError_t mic_launch_abund(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
                             const MicAbund& f, unsigned long long* counts, const uint32_t* status, hipStream_t s);
 
+// ---- score-density counters (mic_density.hip; the rule: mic_density.h) -----------------------------------------------------------
+// An engine's counters while mic_density_start is in force: MIC_DENSITY_WORDS u64 on the engine's device.
+struct MicDensity {
+  unsigned long long* d_counts = nullptr;
+  bool on = false;
+};
+// adds reads [0, n) of `results` to `counts` (MIC_DENSITY_WORDS u64) by the rule of mic_density.h; norm, norm_sub and status as for
+// mic_launch_abund; n_cu caps the grid
+hipError_t mic_launch_density(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
+                              int n_cu, unsigned long long* counts, const uint32_t* status, hipStream_t s);
+
 // ---- rank roll-up (mic_rollup.hip; the rule: mic_rollup.h) ------------------------------------------------------------------------
 // An engine's lineage (mic_rollup_set) and, while mic_rollup_start is in force, its counters.  The lineage's device arrays are one
 // allocation (d_block).

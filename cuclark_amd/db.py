@@ -369,6 +369,24 @@ class MiClarkDB:
         f = filt if filt is not None else host.abund_filter()
         check(self.L.mic_abundance_device(self.h, d_results, d_norm or None, n_reads, C.byref(f), d_counts, stream or None))
 
+    # -- score densities (mic_density_*): u64[MIC_DENSITY_WORDS] = [reads, unassigned, 51 x 101 joint cells] (csrc/mic_density.h)
+    def density_start(self):
+        """Zero and enable the engine's density counters: every ingest batch that returns MIC_INGEST_OK adds its reads."""
+        check(self.L.mic_density_start(self.h))
+
+    def density_fetch(self):
+        """u64[5153]: [0] reads seen, [1] unassigned, [2 + (c - 50) * 101 + g] confidence bin c, gamma bin g (waits for the device)."""
+        out = np.zeros(_lib.MIC_DENSITY_WORDS, np.uint64)
+        check(self.L.mic_density_fetch(self.h, out.ctypes.data, out.size))
+        return out
+
+    def density_stop(self):
+        check(self.L.mic_density_stop(self.h))
+
+    def density_device(self, d_results, d_norm, n_reads, d_counts, stream=0):
+        """The rule on caller-owned device memory: counts ADDED to d_counts (u64[5153]); d_norm 0: every read in gamma bin 0."""
+        check(self.L.mic_density_device(self.h, d_results, d_norm or None, n_reads, d_counts, stream or None))
+
     # -- rank roll-up (mic_rollup_*): a lineage is u16[n_levels, num_targets], level 1 first (host.rollup_check: its two conditions)
     def rollup_set(self, group_of):
         """Install a lineage on the engine (None or an empty array clears it)."""

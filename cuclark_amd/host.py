@@ -135,6 +135,37 @@ def abundance_host(results, norm, k, n_targets, filt=None):
     return counts
 
 
+def density_host(results, norm, k, n_targets, counts=None):
+    """mic_density_host: u64[5153] score-density counters of the result rows (u32[n, 8]) by the rule of csrc/mic_density.h
+    ([0] reads, [1] unassigned, [2 + (c - 50) * 101 + g]).  norm: the CSV's Length column per read, or None (gamma bin 0).
+    counts: an array to ADD to (returned), else a fresh one."""
+    L = _lib.load()
+    results = np.ascontiguousarray(results, np.uint32).reshape(-1, 8)
+    nm = np.ascontiguousarray(norm, np.uint32) if norm is not None else None
+    assert nm is None or nm.size == results.shape[0], "norm: one entry per result row"
+    if counts is None:
+        counts = np.zeros(_lib.MIC_DENSITY_WORDS, np.uint64)
+    assert counts.dtype == np.uint64 and counts.size == _lib.MIC_DENSITY_WORDS and counts.flags.c_contiguous
+    rc = L.mic_density_host(results.ctypes.data, nm.ctypes.data if nm is not None else None, results.shape[0], int(k), int(n_targets),
+                            counts.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_density_host: invalid argument ({rc})")
+    return counts
+
+
+def density_report(counts, which=0):
+    """mic_density_format: the report of exe/cuCLARK --density / exe/evaluate_density (csrc/density_report.hpp) as str.
+    which: 0 all four blocks, 1 totals + confidence, 2 totals + gamma."""
+    L = _lib.load()
+    c = np.ascontiguousarray(counts, np.uint64)
+    n = L.mic_density_format(c.ctypes.data, c.size, int(which), None, 0)
+    if n < 0:
+        raise ValueError(f"mic_density_format: invalid argument ({n})")
+    buf = C.create_string_buffer(n + 1)
+    assert L.mic_density_format(c.ctypes.data, c.size, int(which), buf, n + 1) == n
+    return buf.raw[:n].decode()
+
+
 def rollup_check(n_targets, group_of):
     """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
     1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""

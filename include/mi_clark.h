@@ -524,6 +524,31 @@ int mic_rollup_fetch(mic_engine* e, uint64_t* counts, size_t n);
 int mic_rollup_stop(mic_engine* e);
 int mic_ingest_rollup_rows(mic_engine* e, size_t slot, const uint32_t** rollup, uint64_t* n_reads);
 
+/* ---- score densities: assignments per confidence and per gamma score, counted on the device (CLARK's evaluate_density steps) ----
+ * A read's result row goes into one cell of a 51 x 101 table of bins 0.01 wide (csrc/mic_density.h: the rule, shared by host and
+ * device, exact integer arithmetic): confidence bin c = floor(100 best / (best + second)) in 50 .. 100, gamma bin
+ * g = min(100, floor(100 sum / (norm - k + 1))) in 0 .. 100 (norm - k + 1 <= 0: g = 0); norm as for the abundance profile.
+ *   counters  MIC_DENSITY_WORDS u64: [0] reads seen, [1] unassigned (idxBest == 0 or past the targets), [2 + (c - 50) * 101 + g].
+ * The sum of the cells with c >= 100 conf and g >= 100 gamma is the number of reads the abundance filter {conf, gamma} keeps, for
+ * thresholds of at most two decimals.
+ * mic_density_start / _fetch / _stop   the engine's counters over ingest batches, by the contract of mic_abundance_start / _fetch /
+ *                      _stop (n = MIC_DENSITY_WORDS): a batch that returns MIC_INGEST_OK adds its reads on the device, a batch handed
+ *                      back adds nothing and the caller counts it with mic_density_host.  Freed with the engine.
+ * mic_density_device   the rule on caller-owned device memory: d_results (MIC_RESULT_WORDS u32 per read), d_norm (u32 per read;
+ *                      NULL: every read in gamma bin 0), counts ADDED to d_counts (MIC_DENSITY_WORDS u64).  At most 2^32 - 1 reads
+ *                      per call.  Asynchronous on `stream` (NULL = the engine's stream).
+ * mic_density_host     the rule on the CPU (no device needed): counts added to counts[MIC_DENSITY_WORDS].
+ * mic_density_format   the report of exe/cuCLARK --density and exe/evaluate_density (csrc/density_report.hpp) as text: which = 0 all
+ *                      four blocks, 1 the totals and the confidence block, 2 the totals and the gamma block.  Returns the length of the
+ *                      text (written with a terminator when it fits cap; buf may be NULL to ask for the length) or MIC_E_INVALID. */
+#define MIC_DENSITY_WORDS 5153
+int mic_density_start(mic_engine* e);
+int mic_density_fetch(mic_engine* e, uint64_t* counts, size_t n);
+int mic_density_stop(mic_engine* e);
+int mic_density_device(mic_engine* e, const uint32_t* d_results, const uint32_t* d_norm, size_t n_reads, uint64_t* d_counts, void* stream);
+int mic_density_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets, uint64_t* counts);
+long mic_density_format(const uint64_t* counts, size_t n, int which, char* buf, size_t cap);
+
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */
 int mic_format_ratio_g(uint32_t num, uint32_t den, char* out16);

@@ -201,6 +201,10 @@ int mic_gz_release(mic_engine*) { return MIC_OK; }
 int mic_abundance_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
 int mic_abundance_fetch(mic_engine*, uint64_t* counts, size_t n) { for (size_t i = 0; i < n; ++i) counts[i] = 0; return MIC_OK; }
 int mic_abundance_stop(mic_engine*) { return MIC_OK; }
+// density counters: likewise (mic_density_host is mic_host.cpp's and under test)
+int mic_density_start(mic_engine*) { return MIC_OK; }
+int mic_density_fetch(mic_engine*, uint64_t* counts, size_t n) { for (size_t i = 0; i < n; ++i) counts[i] = 0; return MIC_OK; }
+int mic_density_stop(mic_engine*) { return MIC_OK; }
 // roll-up counters: likewise (the host path's batches are counted by mic_rollup_host, which is mic_host.cpp's and under test)
 int mic_rollup_set(mic_engine*, uint32_t, const uint16_t*) { return MIC_OK; }
 int mic_rollup_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
