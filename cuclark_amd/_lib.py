@@ -115,6 +115,8 @@ SYMBOLS = [
     ("mic_ingest_free", C.c_int, [_VP]),
     ("mic_ingest_set_min_quality", C.c_int, [_VP, C.c_uint32]),
     ("mic_fastq_mask_quality", C.c_int, [_VP, _SZ, C.c_uint32, _VP]),
+    ("mic_ingest_set_low_complexity", C.c_int, [_VP, C.c_uint32]),
+    ("mic_text_mask_low_complexity", C.c_int, [_VP, _SZ, C.c_uint32, _VP]),
     ("mic_gz_inflate_device", C.c_int, [_VP, _VP, _SZ, C.POINTER(_VP), C.POINTER(_SZ), C.POINTER(C.c_uint32)]),
     ("mic_gz_copy_text", C.c_int, [_VP, _VP, _SZ, _SZ, _VP]),
     ("mic_gz_free_text", C.c_int, [_VP, _VP]),

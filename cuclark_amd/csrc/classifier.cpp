@@ -200,6 +200,8 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     if (parts_ > 1) check(mic_db_set_part(e, (uint32_t)(d % parts_), (uint32_t)parts_), "table part");
     // --min-base-quality: every engine masks on its device - in the packer for four-line FASTQ, in the pair merge for two inflated mates
     if (opt_.min_quality_byte) check(mic_ingest_set_min_quality(e, opt_.min_quality_byte), "base-quality threshold");
+    // --mask-low-complexity: every engine masks the batches it owns on its device, in front of the packer
+    if (opt_.low_complexity) check(mic_ingest_set_low_complexity(e, opt_.low_complexity), "low-complexity level");
   }
   if (use > 1) {
     std::cerr << "Devices: " << use << " engine(s) on " << nd_used << " device(s)";

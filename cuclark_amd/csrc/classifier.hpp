@@ -38,6 +38,7 @@ struct Options {
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
   std::string density;                                       // --density <file>: the score densities are counted (mic_density_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
+  uint32_t low_complexity = 0;                               // --mask-low-complexity <level>: DUST level in [1,149], 0 = off (mic_lowc.h)
 };
 
 class Classifier {

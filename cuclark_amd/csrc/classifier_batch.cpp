@@ -105,6 +105,13 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       die("--min-base-quality needs FASTQ records of four lines each (the input's line count is no multiple of four).");
     map = masked.data();
   }
+  // --mask-low-complexity: the same for the rule of mic_lowc.h, once per segment and after the quality mask (FASTA, merged pairs
+  // included, and FASTQ); the device never rewrites a text, so a batch it hands back arrives here unmasked
+  if (opt_.low_complexity) {
+    if (masked.empty()) masked.assign(map, map + nb);
+    if (mic_text_mask_low_complexity(masked.data(), nb, opt_.low_complexity, masked.data()) != MIC_OK) die("--mask-low-complexity: the text could not be masked.");
+    map = masked.data();
+  }
   size_t cap = std::max<size_t>(1024, nb / 96);
   // index arrays live across segments: resizing a fresh vector zero-fills ~200 MB per 512 MB segment
   std::vector<uint64_t>&name_s = ix_[0], &name_e = ix_[1], &seq_s = ix_[2], &seq_e = ix_[3], &length = ix_[4];

@@ -66,6 +66,9 @@ static void print_usage(const char* prog) {
   std::cout << "--min-base-quality <Q> [--quality-offset 33|64],  FASTQ: bases of Phred quality below Q (integer in [1,93]; quality characters\n"
                "                     at offset 33, or 64) are treated as N: they belong to no k-mer.  Length, names and gamma's denominator\n"
                "                     do not change; FASTA input has no qualities and is unaffected\n";
+  std::cout << "--mask-low-complexity <level>,  bases whose surrounding 32-nucleotide window has a DUST score above level/10 (integer in\n"
+               "                     [1,149]; 20 is DUST's customary level) are treated as N: homopolymers and microsatellites belong to\n"
+               "                     no k-mer.  FASTA and FASTQ; Length, names and gamma's denominator do not change\n";
   std::cout << "--tsk, --extended, --light, --htsize <n>, --help, --version\n\n";
 }
 
@@ -160,6 +163,7 @@ int main(int argc, char** argv) {
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
+  long lowc = 0;                         // --mask-low-complexity (0: not given)
   // a whole decimal integer, nothing before or behind it
   auto parse_int = [](const char* s, long& v) {
     if (!*s || strlen(s) > 9) return false;
@@ -225,6 +229,11 @@ int main(int argc, char** argv) {
     if (val == "--min-base-quality") {
       need("Please specify the minimum base quality!");
       if (!parse_int(argv[i], min_q) || min_q < 1 || min_q > 93) { std::cerr << "The minimum base quality should be an integer in [1,93]: " << argv[i] << std::endl; exit(1); }
+      continue;
+    }
+    if (val == "--mask-low-complexity") {
+      need("Please specify the low-complexity level!");
+      if (!parse_int(argv[i], lowc) || lowc < 1 || lowc > 149) { std::cerr << "The low-complexity level should be an integer in [1,149]: " << argv[i] << std::endl; exit(1); }
       continue;
     }
     if (val == "--quality-offset") {
@@ -330,6 +339,7 @@ int main(int argc, char** argv) {
   o.rank_report = rank_report; o.lineage = lineage;
   o.density = density;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
+  o.low_complexity = (uint32_t)lowc;
   mic::Classifier* classifier = nullptr;
   try {
     classifier = new mic::Classifier(o);

@@ -168,6 +168,7 @@ struct mic_engine {
   size_t last_n_reads = 0;
   void* ingest = nullptr;      // device-side ingest state (mic_ingest.hip)
   uint32_t min_quality = 0;    // mic_ingest_set_min_quality: threshold byte of the base-quality mask, 0 = off (mic_qmask.h)
+  uint32_t low_complexity = 0; // mic_ingest_set_low_complexity: level of the low-complexity mask, 0 = off (mic_lowc.h)
   uint64_t reserve_hbm = 0;         // mic_db_reserve_hbm: device memory the caller is allocating while the table builds
   uint32_t part = 0, n_parts = 0;   // mic_db_set_part: this engine answers for part `part` of `n_parts` of the database
   MicAbund abund;                   // mic_abundance_*: the engine's counters (mic_abund.hip)
@@ -611,6 +612,7 @@ int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int
 void** mic_engine_ingest_slot(mic_engine* e) { return &e->ingest; }
 MicAbund* mic_engine_abund(mic_engine* e) { return &e->abund; }
 uint32_t* mic_engine_min_quality(mic_engine* e) { return &e->min_quality; }
+uint32_t* mic_engine_low_complexity(mic_engine* e) { return &e->low_complexity; }
 MicRollup* mic_engine_rollup(mic_engine* e) { return &e->rollup; }
 MicDensity* mic_engine_density(mic_engine* e) { return &e->density; }
 uint32_t mic_engine_row_words(const mic_engine* e) { return e->cfg.row_words; }

@@ -524,6 +524,42 @@ extern "C" int mic_fastq_mask_quality(const uint8_t* in, size_t nb, uint32_t thr
   return MIC_OK;
 }
 
+// ---- low-complexity mask: the rule of mic_lowc.h on the CPU (batches the host path classifies) ---------------------------------------
+#include "mic_lowc.h"
+
+extern "C" int mic_text_mask_low_complexity(const uint8_t* in, size_t nb, uint32_t level, uint8_t* out) {
+  if (!in || !out || nb == 0 || (in[0] != '>' && in[0] != '@') || level > MIC_LOWC_MAX_LEVEL) return MIC_E_INVALID;
+  if (out != in) memmove(out, in, nb);
+  if (level == 0) return MIC_OK;
+  // records as mic_index_reads finds them, walked on the copy: a masked base becomes 'N', which moves no line end and no marker.
+  // Every run is decided from its own bytes before any of them is rewritten, and runs do not overlap: one pass over the original.
+  const bool fasta = in[0] == '>';
+  std::vector<uint8_t> code, flag;
+  for (size_t i = 1;;) {
+    Rec r;
+    i = parse_record(out, nb, fasta, i, r);
+    const size_t e = std::min<size_t>(r.se, nb);
+    for (size_t a = r.ss; a < e;) {
+      if (out[a] == '\n' || mic_lowc_code(out[a]) > 3u) { ++a; continue; }
+      size_t b = a;                                // the run's bytes are [a, b), line ends included
+      code.clear();
+      for (; b < e; ++b) {
+        if (out[b] == '\n') continue;
+        const uint32_t c = mic_lowc_code(out[b]);
+        if (c > 3u) break;
+        code.push_back((uint8_t)c);
+      }
+      flag.resize(code.size());
+      mic_lowc_run(code.data(), code.size(), level, flag.data());
+      for (size_t p = a, j = 0; p < b; ++p) if (out[p] != '\n' && flag[j++]) out[p] = 'N';
+      a = b;
+    }
+    if (fasta) { if (i >= nb) break; ++i; }        // skip '>'
+    else { if (++i >= nb) break; }                 // skip '@'
+  }
+  return MIC_OK;
+}
+
 // ---- rank roll-up: the rule of mic_rollup.h on the CPU (batches the host path classifies, estimate_abundance's cross-check) --------
 #include "mic_rollup.h"
 

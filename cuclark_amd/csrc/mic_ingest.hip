@@ -15,6 +15,7 @@
 #include "mic_internal.h"
 #include "mic_fmt.h"
 #include "mic_qmask.h"
+#include "mic_lowc.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -40,6 +41,7 @@ MicAbund* mic_engine_abund(mic_engine* e);
 MicRollup* mic_engine_rollup(mic_engine* e);
 MicDensity* mic_engine_density(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
+uint32_t* mic_engine_low_complexity(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
 bool mic_peer_enable(int from, int to);
 
@@ -191,7 +193,7 @@ __global__ void __launch_bounds__(256) record_kernel(const uint8_t* __restrict__
   a.seq_s[r] = ss; a.seq_e[r] = ss + nbytes; a.length[r] = len;
   // containers reserved for the read: every part of L >= k nt takes 1 + ceil(L/8) <= 2 + L/8, parts are separated by at
   // least one byte; + slack for a trailing run that is dropped after its first containers were written, + the terminator
-  // (a base masked by its quality, pack_kernel<true>, is still one byte between two parts: the bound holds as it stands)
+  // (a base masked by its quality or by the low-complexity mask is still one byte between two parts: the bound holds as it stands)
   a.bound[r] = (len < (uint32_t)k || status) ? 0u : nbytes / 8 + 2 * (nbytes / (uint32_t)(k + 1) + 1) + 8;
   if (status) atomicOr(&hdr[H_STATUS], status);
   (void)nb;
@@ -207,11 +209,14 @@ __global__ void __launch_bounds__(256) record_kernel(const uint8_t* __restrict__
 // quality line comes from the slot's LINE INDEX, passed in (no new per-record arrays): line 4r + 3, which ends at
 // line_start[4r + 4] - 1 - the virtual line end of an unterminated last line included (lines_finish_kernel).  Both loads are byte
 // loads at consecutive addresses across the wavefront.  <false> is the kernel as it was; every launch without a threshold takes it.
-template <bool QUAL>
+// LOWC (a low-complexity level set, mic_ingest_set_low_complexity): the same lane also takes bit p of the slot's bitmap, which
+// lowc_kernel wrote in front of this kernel (mic_lowc.h), and a set bit is an "other byte" too.  The text itself is never rewritten.
+template <bool QUAL, bool LOWC>
 __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ raw, const uint32_t* __restrict__ seq_s,
                                                    const uint32_t* __restrict__ seq_e, const uint32_t* __restrict__ rp,
                                                    uint16_t* __restrict__ cont, uint32_t n_reads, int k,
-                                                   const uint32_t* __restrict__ line_start, uint32_t c0) {
+                                                   const uint32_t* __restrict__ line_start, uint32_t c0,
+                                                   const uint32_t* __restrict__ lowc) {
   __shared__ uint8_t s_codes[4][80];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -246,6 +251,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ r
         if (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U') { cls = 0; code = (0x4Bu >> (2 * ((u >> 1) & 3u))) & 3u; }
         else cls = b == '\n' ? 1 : 2;
         if (QUAL && mic_qmask_masked(raw + qs, qn, p - s, c0)) cls = 2;
+        if (LOWC && ((lowc[p >> 5] >> (p & 31u)) & 1u)) cls = 2;
       }
       const uint64_t m_nt = __ballot(cls == 0), m_ot = __ballot(cls == 2);
       int lo = 0;
@@ -281,6 +287,88 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ r
     }
     close_run();
     if (lane == 0 && hdr < o1 - o0) out[hdr] = 0;
+  }
+}
+
+// ---- the low-complexity mask (mic_lowc.h): one wavefront per read, between record_kernel and pack_kernel -----------------
+// Writes bit p of `bits` (zeroed in front of the launch) for every masked base at text offset p; the text is not touched.
+// The read's bytes are taken 64 at a time as the packer takes them.  '\n' is dropped by ballot / popcount, what is left (a nucleotide's
+// 2-bit code, or 4 for a byte that ends the run) goes into a ring of 256 LOGICAL positions per wavefront with the text offset beside it.
+// Whenever 80 undecided positions are in the ring (64 + the 16 a window looks ahead; at the read's end: what is left), 64 of them are
+// decided, one per lane: six ballots turn the 96 ring entries around them into three 128-bit masks (run end, low and high code bit),
+// every lane shifts its own 32-bit window out of them - the nearest run ends on either side clip it - and counts equal triplets at
+// every distance 1..29 with shifts, ANDs and popcounts of those three words (mic_lowc_T_planes): no histogram, no LDS traffic and no
+// cross-lane step inside the count; about 12 vector instructions per distance.  Ring: an entry is read until it is 16 behind the
+// decided front and written up to 143 ahead of it, 160 < 256 apart.  QUAL: a base masked by its quality ends the run (the rule is
+// applied to the quality-masked text).  Reads of which nothing is packed (rp[r] == rp[r + 1]: shorter than k, or a batch that goes
+// back to the host) are skipped.
+template <bool QUAL>
+__global__ void __launch_bounds__(256) lowc_kernel(const uint8_t* __restrict__ raw, const uint32_t* __restrict__ seq_s,
+                                                   const uint32_t* __restrict__ seq_e, const uint32_t* __restrict__ rp, uint32_t n_reads,
+                                                   uint32_t level, const uint32_t* __restrict__ line_start, uint32_t c0,
+                                                   uint32_t* __restrict__ bits) {
+  __shared__ uint8_t s_code[4][256];
+  __shared__ uint32_t s_pos[4][256];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* ring_c = s_code[wv];
+  uint32_t* ring_p = s_pos[wv];
+  const uint32_t n_waves = gridDim.x * 4;
+  for (uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv); r < n_reads; r += n_waves) {
+    if (rp[r + 1] == rp[r]) continue;
+    const uint32_t s = seq_s[r], e = seq_e[r];
+    uint32_t qs = 0, qn = 0;
+    if (QUAL) { qs = line_start[4 * r + 3]; qn = line_start[4 * r + 4] - 1u - qs; }
+    uint32_t produced = 0, consumed = 0;          // logical positions in the ring so far; decided so far (both wave-uniform)
+    auto decide = [&]() {                         // logical positions [consumed, consumed + 64), lane by lane
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      // ring entries consumed - 16 + i, i in [0, 96): lane i holds entry i, lanes 0..31 entry 64 + i as well; what lies in front of
+      // the read or behind what was produced (only at the read's end) ends a run
+      const uint32_t qa = consumed - 16u + (uint32_t)lane, qb = qa + 64u;      // (qa wraps below 0: not < produced)
+      uint32_t ca = 4, cb = 4;
+      if (qa < produced) ca = ring_c[qa & 255u];
+      if (lane < 32 && qb < produced) cb = ring_c[qb & 255u];
+      const uint64_t e_lo = __ballot(ca > 3u), e_hi = __ballot(cb > 3u);
+      const uint64_t a_lo = __ballot((ca & 1u) != 0), a_hi = __ballot((cb & 1u) != 0);
+      const uint64_t b_lo = __ballot((ca & 2u) != 0), b_hi = __ballot((cb & 2u) != 0);
+      auto window = [&](uint64_t lo, uint64_t hi) { return lane ? (uint32_t)((lo >> lane) | (hi << (64 - lane))) : (uint32_t)lo; };
+      const uint32_t we = window(e_lo, e_hi), w0 = window(a_lo, a_hi), w1 = window(b_lo, b_hi);   // bit i: position q - 16 + i
+      const uint32_t q = consumed + (uint32_t)lane;
+      if (q < produced && !((we >> 16) & 1u)) {
+        const uint32_t below = we & 0xFFFFu, above = we >> 17;
+        const uint32_t lo = below ? 32u - (uint32_t)__clz((int)below) : 0u;
+        const uint32_t hi = above ? 16u + (uint32_t)__ffs((int)above) : 32u;
+        if (hi - lo >= 4u) {
+          const uint32_t l = hi - lo - 2u;
+          if (mic_lowc_over(mic_lowc_T_planes(w0, w1, lo, l), l, level)) {
+            const uint32_t p = ring_p[q & 255u];
+            atomicOr(&bits[p >> 5], 1u << (p & 31u));
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      consumed += 64u;
+    };
+    for (uint32_t base = s; base < e; base += 64) {
+      const uint32_t p = base + lane;
+      uint32_t code = 5;                          // 0..3 nucleotide, 4 ends the run, 5 line end or past the end: no logical position
+      if (p < e) {
+        const uint32_t b = raw[p];
+        if (b != '\n') {
+          code = mic_lowc_code(b);
+          if (QUAL && mic_qmask_masked(raw + qs, qn, p - s, c0)) code = 4;
+        }
+      }
+      const uint64_t m = __ballot(code < 5u);
+      if (code < 5u) {
+        const uint32_t idx = (produced + (uint32_t)__popcll(m & ((1ull << lane) - 1))) & 255u;
+        ring_c[idx] = (uint8_t)code; ring_p[idx] = p;
+      }
+      produced += (uint32_t)__popcll(m);
+      while (produced - consumed >= 80u) decide();
+    }
+    while (consumed < produced) decide();
   }
 }
 
@@ -524,6 +612,7 @@ struct Slot {
   RecArrays rec{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t* d_rp = nullptr; uint16_t* d_cont = nullptr; uint32_t* d_results = nullptr; uint32_t* d_flagged = nullptr;
   uint32_t* d_crowd = nullptr;   // work area of the crowded runs' follow-up (mic_internal.h: mic_crowd_dims)
+  uint32_t* d_lowc = nullptr;    // low-complexity bitmap, one bit per text byte (mic_lowc.h); allocated with the first batch that has a level set
   uint32_t* d_line_len = nullptr; uint32_t* d_line_off = nullptr; char* d_csv = nullptr; uint32_t* d_hdr = nullptr;
   void* d_tmp = nullptr; size_t tmp_bytes = 0;
   hipStream_t stream = nullptr;
@@ -1068,6 +1157,8 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   // the base-quality threshold of the slot's engine (0: none): four-line FASTQ is then packed by pack_kernel<true>
   const uint32_t c0 = *mic_engine_min_quality(e);
   if (c0 && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while a base-quality threshold is set: the quality lines are gone");
+  // the low-complexity level of the slot's engine (0: none): lowc_kernel marks the masked bases, pack_kernel<*, true> skips them
+  const uint32_t lc = *mic_engine_low_complexity(e);
   Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
   if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
   if (n_bytes == 0 || n_bytes > g->max_bytes) return mic_set_error(MIC_E_INVALID, "batch of %zu bytes does not fit the slot (%zu)", n_bytes, g->max_bytes);
@@ -1130,8 +1221,21 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   {
     unsigned blocks = (n_reads + 3) / 4, cap = (unsigned)ncu * 64u;
     if (blocks > cap) blocks = cap;
-    if (c0 && !fasta) pack_kernel<true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0);
-    else pack_kernel<false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u);
+    const bool qual = c0 && !fasta;
+    if (lc) {
+      if (!s.d_lowc) {   // the slot's first batch that is masked: one bit per byte of the slot's text; it goes with the slot
+        void* d = nullptr;
+        ITRY(hipMalloc(&d, g->max_bytes / 8 + 64));
+        s.dev_allocs.push_back(d);
+        s.d_lowc = (uint32_t*)d;
+      }
+      ITRY(hipMemsetAsync(s.d_lowc, 0, ((size_t)nb + 31) / 32 * 4, st));
+      if (qual) lowc_kernel<true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, n_reads, lc, s.d_line_start, c0, s.d_lowc);
+      else lowc_kernel<false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, n_reads, lc, nullptr, 0u, s.d_lowc);
+      if (qual) pack_kernel<true, true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0, s.d_lowc);
+      else pack_kernel<false, true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u, s.d_lowc);
+    } else if (qual) pack_kernel<true, false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0, nullptr);
+    else pack_kernel<false, false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u, nullptr);
   }
   // rank roll-up started on the slot's engine: the rows instantiation of the same kernel fills the slot's row buffer.  One engine:
   // rows of the --extended width, so that a batch is handed back exactly when it is handed back without roll-up (a row that does
@@ -1221,6 +1325,13 @@ int mic_ingest_set_min_quality(mic_engine* e, uint32_t threshold_byte) {
   if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   if (threshold_byte > 255) return mic_set_error(MIC_E_INVALID, "a threshold byte is 0 (off) .. 255, got %u", threshold_byte);
   *mic_engine_min_quality(e) = threshold_byte;
+  return MIC_OK;
+}
+
+int mic_ingest_set_low_complexity(mic_engine* e, uint32_t level) {
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  if (level > MIC_LOWC_MAX_LEVEL) return mic_set_error(MIC_E_INVALID, "a low-complexity level is 0 (off) .. %u, got %u", MIC_LOWC_MAX_LEVEL, level);
+  *mic_engine_low_complexity(e) = level;
   return MIC_OK;
 }
 

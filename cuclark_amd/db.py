@@ -315,6 +315,11 @@ class MiClarkDB:
         below q (quality characters at `offset`, 33 or 64) take no part in any k-mer; q = 0 clears it."""
         check(self.L.mic_ingest_set_min_quality(self.h, (int(offset) + int(q)) if q else 0))
 
+    def ingest_set_low_complexity(self, level):
+        """Low-complexity mask of this engine's ingest (mic_ingest_set_low_complexity): bases whose 32-nucleotide window has a DUST
+        score above level / 10 take no part in any k-mer (csrc/mic_lowc.h); level in [1, 149], 20 is customary, 0 clears it."""
+        check(self.L.mic_ingest_set_low_complexity(self.h, int(level)))
+
     def ingest_classify(self, slot, data, paired=False, csv=True, flags=0):
         """data: bytes of whole records.  Returns dict(status, n_reads, csv (bytes), results (u32[n,8] or None)).
         csv=False: MIC_INGEST_NO_CSV (no CSV text, csv is b""); flags: further MIC_INGEST_* flags."""

@@ -112,6 +112,18 @@ def mask_quality(data, q, offset=33, threshold_byte=None):
     return out[: src.size].tobytes()
 
 
+def mask_low_complexity(data, level):
+    """mic_text_mask_low_complexity: the bytes of FASTA or four-line FASTQ text with every base whose 32-nucleotide window has a DUST
+    score above level / 10 replaced by 'N' - csrc/mic_lowc.h's rule on the CPU; level 0: a plain copy.
+    ValueError when the text does not start with '>' or '@', or the level is above 149."""
+    src = np.frombuffer(bytes(data), np.uint8)
+    out = np.empty(max(src.size, 1), np.uint8)
+    rc = _lib.load().mic_text_mask_low_complexity(src.ctypes.data if src.size else None, src.size, int(level), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_text_mask_low_complexity: not FASTA / FASTQ text, or a level above 149 ({rc})")
+    return out[: src.size].tobytes()
+
+
 def abund_filter(confidence="0.5", gamma="0"):
     """mic_abund_filter from decimal strings (CLARK's defaults: -c 0.5 -g 0)."""
     cn, cd = parse_threshold(confidence)

@@ -356,6 +356,30 @@ int mic_ingest_free(mic_engine* e);
  *                             is written then.  For what stays on the host: batches handed back (MIC_INGEST_FALLBACK), the batch path. */
 int mic_ingest_set_min_quality(mic_engine* e, uint32_t threshold_byte);
 int mic_fastq_mask_quality(const uint8_t* in, size_t nb, uint32_t threshold_byte, uint8_t* out);
+/* ---- low-complexity mask: bases inside homopolymer / microsatellite sequence take no part in any k-mer (csrc/mic_lowc.h: the rule) --
+ * CLARK databases are built from unmasked genomes, so a poly-A tail or an (AC)n tract of a read is probed like any other sequence; the
+ * reference has no such mask.  A RUN is a maximal sequence of ACGTU bytes (either case) of a record's sequence - the packer's part
+ * before its length test: '\n' is transparent (wrapped FASTA lines join), every other byte ends it ('\r', 'N', a base masked by the
+ * base-quality mask: runs are taken after that mask).  With the run's n nucleotides x[0..n) in the packer's 2-bit code and triplets
+ * t[j] = 16 x[j] + 4 x[j+1] + x[j+2], the WINDOW of base i is [lo, hi) = [max(0, i-16), min(n, i+16)): width 32, centred, clipped to
+ * the run, never across an 'N', the joint of a merged pair or a record end.  l = hi - lo - 2 triplets t[lo .. lo+l) lie in it, c_v of
+ * them have the value v, T = sum_v c_v (c_v - 1) / 2.  Base i is MASKED iff l >= 2 and 10 T > level (l - 1): DUST's score above
+ * level / 10, on a fixed window of about k nucleotides - not symmetric DUST's perfect intervals, so another tool's report differs at
+ * tract edges.  Level 20 is DUST's customary level.  A masked base is to the packer what an 'N' is; Length column, names and gamma's
+ * denominator do not change: the result is that of the same text with every masked base replaced by 'N', byte for byte.  The rule is
+ * not idempotent (what is left between two masked stretches is a new, shorter run): it is applied once, to the original text.
+ * mic_ingest_set_low_complexity  engine state; 0 clears it, a level above 149 is MIC_E_INVALID (150 could mask nothing).  From then on
+ *                                it applies to every mic_ingest_classify / mic_ingest_classify_group call owned by this engine: FASTA
+ *                                (merged pairs included), four-line FASTQ and MIC_INGEST_FASTQ_2LINE text, uploaded or resident.  A
+ *                                kernel in front of the packer writes one bit per text byte into a bitmap of the slot (allocated with
+ *                                the slot's first such batch); the slot's text is not rewritten, so a resident text can be classified
+ *                                again.  With the level 0 nothing is launched and nothing is allocated.
+ * mic_text_mask_low_complexity   the rule on the CPU, no device needed: a copy of FASTA or four-line FASTQ text with the masked bases
+ *                                replaced by 'N' (in == out is allowed; level 0: a plain copy); records are those of mic_index_reads.
+ *                                Linear in the text.  MIC_E_INVALID, nothing written, when the text does not start with '>' or '@' or
+ *                                the level is above 149.  For what stays on the host: batches handed back, the batch path. */
+int mic_ingest_set_low_complexity(mic_engine* e, uint32_t level);
+int mic_text_mask_low_complexity(const uint8_t* in, size_t nb, uint32_t level, uint8_t* out);
 /* ---- compressed input: one gzip member inflated on the device ------------------------------------------------
  * Replaces the `gunzip` the reference's scripts run in front of the classifier (classify_metagenome.sh:116-142) for the
  * common cases: ONE member without a preset dictionary (what `gzip` writes), or a whole block-gzip file (BGZF: members with a

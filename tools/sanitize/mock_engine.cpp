@@ -58,6 +58,7 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
 int mic_ingest_free(mic_engine* e) { if (e) { e->raw.clear(); e->csv.clear(); } return MIC_OK; }
 // (the mock's CSV is name and length, which a masked base does not change)
 int mic_ingest_set_min_quality(mic_engine*, uint32_t threshold_byte) { return threshold_byte > 255 ? MIC_E_INVALID : MIC_OK; }
+int mic_ingest_set_low_complexity(mic_engine*, uint32_t level) { return level > 149 ? MIC_E_INVALID : MIC_OK; }
 
 int mic_ingest_classify(mic_engine* e, size_t slot, size_t n_bytes, int flags, mic_ingest_result* out) {
   memset(out, 0, sizeof(*out));
