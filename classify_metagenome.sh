@@ -3,10 +3,10 @@
 # it reads the targets definition and database directory from ./.settings (written by set_targets.sh as
 # "-T <targets file>" and "-D <database directory>/"), appends the user's options, and runs exe/cuCLARK, or
 # exe/cuCLARK-l when --light is given.  --gzipped is accepted and needs no temporary copy: the binary inflates
-# gzip input itself.  Every other option (--min-base-quality Q, --quality-offset 33|64, --mask-low-complexity <level>, --abundance ..., --rank-report ..., --density <file>) goes to the binary as given.
+# gzip input itself.  Every other option (--min-base-quality Q, --quality-offset 33|64, --mask-low-complexity <level>, --abundance ..., --rank-report ..., --density <file>, --classified-out <file>, --unclassified-out <file>) goes to the binary as given.
 DIR=$(dirname "$0")
 if [ $# -lt 1 ]; then
-  echo "Usage: $0 -O <objects> | -P <mate1> <mate2>  -R <results> [-k n] [-n threads] [-b batches] [-d gpus] [--light] [--gzipped] [--extended] [--min-base-quality Q [--quality-offset 33|64]] [--mask-low-complexity <level>] [--abundance <file>] [--density <file>] ..."
+  echo "Usage: $0 -O <objects> | -P <mate1> <mate2>  -R <results> [-k n] [-n threads] [-b batches] [-d gpus] [--light] [--gzipped] [--extended] [--min-base-quality Q [--quality-offset 33|64]] [--mask-low-complexity <level>] [--abundance <file>] [--density <file>] [--classified-out <file>] [--unclassified-out <file>] ..."
   exit 0
 fi
 if [ ! -f ./.settings ]; then

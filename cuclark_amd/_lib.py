@@ -59,6 +59,7 @@ MIC_INGEST_OK, MIC_INGEST_FALLBACK, MIC_INGEST_ODD_RECORD, MIC_INGEST_TRUNCATED 
 MIC_INGEST_LONG_READ, MIC_INGEST_TOO_MANY, MIC_INGEST_DENSE = 8, 16, 32
 MIC_INGEST_FASTQ_2LINE = 2      # ingest flag: FASTQ records of header + sequence line only
 MIC_INGEST_NO_CSV = 16          # ingest flag (not a status bit): no CSV kernels, no text back
+MIC_SPLIT_CLASSIFIED, MIC_SPLIT_UNCLASSIFIED = 1, 2
 
 
 class MicAbundFilter(C.Structure):
@@ -161,6 +162,12 @@ SYMBOLS = [
     ("mic_density_device", C.c_int, [_VP, _VP, _VP, _SZ, _VP, _VP]),
     ("mic_density_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, _VP]),
     ("mic_density_format", C.c_long, [_VP, _SZ, C.c_int, C.c_char_p, _SZ]),
+    ("mic_split_start", C.c_int, [_VP, C.POINTER(MicAbundFilter), C.c_int]),
+    ("mic_split_stop", C.c_int, [_VP]),
+    ("mic_ingest_split_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_VP),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("mic_split_device", C.c_int, [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP, C.POINTER(MicAbundFilter), C.c_int, _VP, _U64P, _VP]),
+    ("mic_split_host", C.c_int, [_VP, _SZ, _U64P, _SZ, _VP, _VP, C.c_int, C.c_uint32, C.POINTER(MicAbundFilter), C.c_int, _VP, _U64P]),
     ("mic_format_ratio_g", C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p]),
     ("mic_key_bytes_rule", C.c_int, [C.c_uint64, C.c_int]),
     ("mic_index_reads", C.c_long, [_VP, _SZ, _SZ, _U64P, _U64P, _U64P, _U64P, _U64P]),

@@ -202,6 +202,9 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     if (opt_.min_quality_byte) check(mic_ingest_set_min_quality(e, opt_.min_quality_byte), "base-quality threshold");
     // --mask-low-complexity: every engine masks the batches it owns on its device, in front of the packer
     if (opt_.low_complexity) check(mic_ingest_set_low_complexity(e, opt_.low_complexity), "low-complexity level");
+    // --classified-out / --unclassified-out: started before the slots are allocated, so that their split buffers are pinned with them
+    // (while the database loads), not with every slot's first batch inside the timed region
+    if (splitting()) check(mic_split_start(e, &opt_.abund_filter, splitting()), "read splitting");
   }
   if (use > 1) {
     std::cerr << "Devices: " << use << " engine(s) on " << nd_used << " device(s)";
@@ -254,6 +257,7 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
 }
 
 void Classifier::reset_counts() {
+  if (splitting()) for (mic_engine* e : engines_) check(mic_split_start(e, &opt_.abund_filter, splitting()), "read splitting");
   if (ranking()) {
     for (mic_engine* e : engines_) check(mic_rollup_start(e, &opt_.abund_filter), "roll-up counters");
     std::lock_guard<std::mutex> lk(count_mu_);
@@ -380,6 +384,15 @@ bool merge_paired_parallel(const std::string& file1, const std::string& file2, u
   return !feed.gave_up();
 }
 
+bool Classifier::list_mode(const std::string& objects, const std::string& results) {
+  if (!file_exists(results)) return false;
+  GzLines in(objects);
+  std::string line;
+  in.line(line);
+  std::vector<std::string> ele = split_seps(line, " \t,");
+  return !((!line.empty() && (line[0] == '>' || line[0] == '@')) || ele.size() == 2);
+}
+
 void Classifier::run(const std::string& objects, const std::string& results) {
   auto simple = [&](const std::string& obj, const std::string& res) {
     if (is_gzip(obj) && device_ingest()) {
@@ -453,11 +466,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
     simple(objects, results);
     return;
   }
-  GzLines in(objects);
-  std::string line;
-  in.line(line);
-  std::vector<std::string> ele = split_seps(line, " \t,");
-  if ((!line.empty() && (line[0] == '>' || line[0] == '@')) || ele.size() == 2) {
+  if (!list_mode(objects, results)) {
     std::cout << "Processing file'" << objects << "' in " << opt_.batches << " batches using " << opt_.threads
               << " CPU thread(s)." << std::endl;
     simple(objects, results);
@@ -467,6 +476,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");
+  if (splitting()) die("--classified-out / --unclassified-out do not take list-of-files mode: classify the files one at a time.");
   std::ifstream o_fd(objects), r_fd(results);
   std::string o_line, r_line;
   std::cout << "Using " << opt_.threads << " CPU thread(s)." << std::endl;

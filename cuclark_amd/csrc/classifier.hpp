@@ -38,6 +38,7 @@ struct Options {
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
   std::string density;                                       // --density <file>: the score densities are counted (mic_density_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
+  std::string classified_out, unclassified_out;              // --classified-out / --unclassified-out <file>: the reads themselves, split (mic_split_*)
   uint32_t low_complexity = 0;                               // --mask-low-complexity <level>: DUST level in [1,149], 0 = off (mic_lowc.h)
 };
 
@@ -97,6 +98,9 @@ class Classifier {
   std::vector<uint64_t> density_counts();
   const rank::Lineage& lineage() const { return lineage_; }
 
+  // --classified-out / --unclassified-out: is `objects` with `results` a list-of-files run?  (no device needed: asked before one is touched)
+  static bool list_mode(const std::string& objects, const std::string& results);
+
   std::string db_name() const;  // getdbName, CuCLARK_hh.hh:580-591
   const std::vector<std::string>& target_names() const { return names_; }
 
@@ -129,6 +133,12 @@ class Classifier {
   bool counting() const { return !opt_.abundance.empty(); }
   bool ranking() const { return !opt_.rank_report.empty(); }
   bool densing() const { return !opt_.density.empty(); }
+  // --classified-out / --unclassified-out: the classes asked for (0: none).  The streaming path takes the split text from the engines
+  // (mic_ingest_split_text); what stays on the host is split by mic_split_host in process_segment, into the run's files or - a batch
+  // the streaming path handed back - into the two sinks
+  int splitting() const { return (opt_.classified_out.empty() ? 0 : MIC_SPLIT_CLASSIFIED) | (opt_.unclassified_out.empty() ? 0 : MIC_SPLIT_UNCLASSIFIED); }
+  int split_fd_[2] = {-1, -1};                // run_segments: the two files, written in order
+  std::string* split_sink_[2] = {nullptr, nullptr};
   rank::Lineage lineage_;
   std::vector<uint64_t> host_rollup_;
   void reset_counts();

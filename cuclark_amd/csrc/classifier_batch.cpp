@@ -39,6 +39,15 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
   csv_out_ = !results_base.empty();               // (no -R: a summary-only --abundance run writes no result CSV)
   FILE* fout = csv_out_ ? fopen(csv.c_str(), "w") : nullptr;
   if (csv_out_ && !fout) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return; }
+  // --classified-out / --unclassified-out: the two files, created even when they stay empty; process_segment appends in order
+  const std::string* split_name[2] = {&opt_.classified_out, &opt_.unclassified_out};
+  for (int c = 0; c < 2; ++c) {
+    split_fd_[c] = -1;
+    if (split_name[c]->empty()) continue;
+    unlink(split_name[c]->c_str());
+    split_fd_[c] = open(split_name[c]->c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    if (split_fd_[c] == -1) { std::cerr << "Failed to create/open file: " << *split_name[c] << std::endl; if (fout) fclose(fout); if (c && split_fd_[0] != -1) { close(split_fd_[0]); split_fd_[0] = -1; } return; }
+  }
   reset_counts();
   struct timeval t0, t1;
   gettimeofday(&t0, nullptr);
@@ -73,6 +82,8 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
   // a full disk shows here at the latest (the command line leaves through _exit: nothing later would flush or report it)
   const bool write_failed = fout && ferror(fout) != 0;
   if (fout && (fclose(fout) != 0 || write_failed)) { if (err.empty()) err = "cannot write " + csv + " (disk full?)"; }
+  for (int c = 0; c < 2; ++c)
+    if (split_fd_[c] != -1) { if (close(split_fd_[c]) != 0 && err.empty()) err = "cannot write " + *split_name[c] + " (disk full?)"; split_fd_[c] = -1; }
   release_batches();
   if (!err.empty()) die(err);
   gettimeofday(&t1, nullptr);
@@ -98,6 +109,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
   if (nb == 0 || (map[0] != '>' && map[0] != '@')) { std::cerr << "Failed to recognize the format of the file." << std::endl; exit(-1); }
   // --min-base-quality: what is classified on the host is masked on the host, by the same rule (mic_qmask.h) - a copy of the FASTQ
   // text with 'N' for every masked base; merged pairs arrive masked (they are FASTA text)
+  const uint8_t* const original = map;        // (--classified-out / --unclassified-out copy the records as they came, whatever is masked)
   std::vector<uint8_t> masked;
   if (opt_.min_quality_byte && map[0] == '@') {
     masked.resize(nb);
@@ -165,6 +177,9 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
   const uint32_t row_words = row_words_;
   const size_t line_cap = 512 + (opt_.extended ? (size_t)T * 12 : 0);
 
+  // --classified-out / --unclassified-out: every read's result row as the CSV shows it and its Length column, for mic_split_host below
+  const int split = paired ? 0 : splitting();
+  std::vector<uint32_t> sp_res(split ? N * MIC_RESULT_WORDS : 0), sp_norm(split ? N : 0);
   double t_pack = 0, t_query = 0, t_format = 0, t_write = 0;   // thread-seconds, MIC_CLI_TIMING only
   auto now_s = [] { struct timeval t; gettimeofday(&t, nullptr); return t.tv_sec + t.tv_usec / 1e6; };
 #ifdef _OPENMP
@@ -240,6 +255,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
           }
           dn = dense.data();
         }
+        if (split) { memcpy(&sp_res[r * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4); sp_norm[r] = (uint32_t)length[r]; }
         if (counting() || densing()) memcpy(&ab_res[i * MIC_RESULT_WORDS], rr, MIC_RESULT_WORDS * 4);
         if (counting() || ranking() || densing()) ab_norm[i] = (uint32_t)(paired ? length[r] - 1 : length[r]);      // (the CSV's Length column, CuCLARK_hh.hh:2119)
         if (ranking() && dn)
@@ -279,6 +295,25 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
     std::cerr << "[timing]   thread-seconds: pack " << t_pack << ", copy+query+wait " << t_query << ", format " << t_format
               << ", ordered write " << t_write << std::endl;
   if (!err.empty()) die(err);
+  if (split) {       // the segment's ORIGINAL bytes, cut at the host indexer's records (mic_split.h)
+    std::vector<uint64_t> start(N);
+    for (size_t r = 0; r < N; ++r) start[r] = name_s[r] - 1;
+    std::vector<uint8_t> part(nb + 1);
+    uint64_t tot[4] = {0, 0, 0, 0};
+    if (mic_split_host(original, nb, start.data(), N, sp_res.data(), sp_norm.data(), k, T, &opt_.abund_filter, split, part.data(), tot) != MIC_OK)
+      die("--classified-out / --unclassified-out: the records of the input do not tile it (a record the reader does not take as it is).");
+    const uint8_t* piece[2] = {part.data(), part.data() + tot[0]};
+    for (int c = 0; c < 2; ++c) {
+      if (!(split & (1 << c))) continue;
+      const size_t n = (size_t)tot[c];
+      if (sink_) { if (split_sink_[c]) split_sink_[c]->append((const char*)piece[c], n); continue; }
+      for (size_t done = 0; done < n;) {
+        const ssize_t w = write(split_fd_[c], piece[c] + done, n - done);
+        if (w <= 0) die("cannot write " + (c ? opt_.unclassified_out : opt_.classified_out) + " (disk full?)");
+        done += (size_t)w;
+      }
+    }
+  }
   return N;
 }
 

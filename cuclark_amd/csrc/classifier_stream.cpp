@@ -32,7 +32,8 @@ void Classifier::ingest_geometry(size_t total_bytes, size_t& bytes, size_t& work
   if (const char* env = getenv("MIC_INGEST_WORKERS")) { long v = atol(env); if (v >= 1 && v <= 64) workers = (size_t)v; }
   // --min-base-quality: FASTQ travels with its quality lines (the device masks from them), twice the bytes per read: slots of twice
   // the size hold the batches they held before (128 MiB is mic_ingest_alloc's limit)
-  if (opt_.min_quality_byte) bytes = std::min<size_t>(bytes * 2, (size_t)128 << 20);
+  // (--classified-out / --unclassified-out: the same - the records are handed back whole, so they travel whole)
+  if (opt_.min_quality_byte || splitting()) bytes = std::min<size_t>(bytes * 2, (size_t)128 << 20);
   // small inputs: do not pin more than the input needs
   while (bytes > (1u << 20) && total_bytes / workers < bytes / 2) bytes /= 2;
   if (total_bytes < bytes) workers = 1;
@@ -215,6 +216,23 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
     out_fd = open(csv.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
     if (out_fd == -1) { std::cerr << "Failed to create/open file result: " << csv << std::endl; return true; }
   }
+  // --classified-out / --unclassified-out: the two files, created even when they stay empty; the writer puts every batch's split texts
+  // at the offsets the batch's turn gives them, like the CSV
+  const int split = paired ? 0 : splitting();
+  const bool writing = !summary || split != 0;
+  const std::string* split_name[2] = {&opt_.classified_out, &opt_.unclassified_out};
+  int split_fd[2] = {-1, -1};
+  for (int c = 0; c < 2; ++c) {
+    if (!(split & (1 << c))) continue;
+    unlink(split_name[c]->c_str());
+    split_fd[c] = open(split_name[c]->c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    if (split_fd[c] == -1) {
+      std::cerr << "Failed to create/open file: " << *split_name[c] << std::endl;
+      if (out_fd != -1) close(out_fd);
+      if (c && split_fd[0] != -1) close(split_fd[0]);
+      return true;
+    }
+  }
   reset_counts();
   struct timeval t0, t1;
   gettimeofday(&t0, nullptr);
@@ -231,7 +249,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   const uint64_t t0_us = (uint64_t)t0.tv_sec * 1000000u + (uint64_t)t0.tv_usec;
   { struct timeval t; gettimeofday(&t, nullptr); ts_alloc = (uint64_t)t.tv_sec * 1000000u + (uint64_t)t.tv_usec; }
   n_objects_ = 0;
-  uint64_t out_off = 0;
+  uint64_t out_off = 0, split_off[2] = {0, 0};
   if (!summary) {  // header (CuCLARK_hh.hh:1957-1972)
     std::vector<const char*> nm(names_.size());
     for (size_t t = 0; t < names_.size(); ++t) nm[t] = names_[t].c_str();
@@ -258,15 +276,18 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   if (const char* env = getenv("MIC_INGEST_NW")) { long v = atol(env); if (v >= 1 && v <= 32) NW = (size_t)v; }
   size_t NL = T > ND + NW ? T - ND - NW : 1;
   if (S == 1) { ND = NW = NL = 1; }
-  if (summary && S > 1) NL += NW;     // (no writer: its share of the threads loads)
+  if (!writing && S > 1) NL += NW;    // (no writer: its share of the threads loads)
   // (--min-base-quality: whole four-line records are uploaded, the packer reads the quality lines)
-  const bool strip_ok = getenv("MIC_KEEP_QUALITY") == nullptr && opt_.min_quality_byte == 0;
+  // (--classified-out / --unclassified-out: whole records are uploaded, the device hands them back as they came)
+  const bool strip_ok = getenv("MIC_KEEP_QUALITY") == nullptr && opt_.min_quality_byte == 0 && !split;
   const bool timing = getenv("MIC_CLI_TIMING") != nullptr;
 
   struct Item {
     size_t id = 0, slot = 0; Range r; size_t n = 0; int flags = 0; bool host = false;      // loader -> device
     const char* text = nullptr; size_t text_n = 0, reads = 0; uint64_t off = 0;             // device -> writer
     std::shared_ptr<std::string> own;                                                      // CSV of a host-path batch
+    const uint8_t* sp_text[2] = {nullptr, nullptr}; size_t sp_n[2] = {0, 0}; uint64_t sp_off[2] = {0, 0};   // the classified / unclassified records
+    std::shared_ptr<std::string> sp_own[2];                                                // ... of a host-path batch
     uint64_t ts[6] = {0, 0, 0, 0, 0, 0};   // MIC_CLI_TRACE: slot taken / loaded / device start / device end / write start / write end (us since start)
   };
   const bool trace = getenv("MIC_CLI_TRACE") != nullptr;
@@ -388,7 +409,14 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
           if (parts_ == 1) check(mic_ingest_classify(engines_[eng], slots[it.slot].slot, it.n, it.flags, &res), "device ingest");
           else check(mic_ingest_classify_group(engines_.data() + eng / parts_ * parts_, parts_, eng % parts_, slots[it.slot].slot, it.n, it.flags, &res),
                      "device ingest (table-sharded)");
-          if (res.status == MIC_INGEST_OK) { it.text = res.csv; it.text_n = (size_t)res.csv_bytes; it.reads = (size_t)res.n_reads; }
+          if (res.status == MIC_INGEST_OK) {
+            it.text = res.csv; it.text_n = (size_t)res.csv_bytes; it.reads = (size_t)res.n_reads;
+            if (split) {       // pointers into the slot's pinned split buffer: valid until the writer frees the slot
+              uint64_t nc = 0, nu = 0;
+              check(mic_ingest_split_text(engines_[eng], slots[it.slot].slot, &it.sp_text[0], &nc, nullptr, &it.sp_text[1], &nu, nullptr), "split text");
+              it.sp_n[0] = (size_t)nc; it.sp_n[1] = (size_t)nu;
+            }
+          }
           else it.host = true;
         }
         if (!failed && it.host) {   // the host indexer / packer / CSV writer on the ORIGINAL bytes of the range (rare: one at a time)
@@ -398,16 +426,18 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
           std::lock_guard<std::mutex> lk(host_mu);
           ++n_fallback;
           sink_ = it.own.get();
+          for (int c = 0; c < 2; ++c) { it.sp_own[c] = std::make_shared<std::string>(); split_sink_[c] = it.sp_own[c].get(); }
           try { it.reads = process_segment((const uint8_t*)bytes.data(), bytes.size(), paired, nullptr); } catch (...) { sink_ = nullptr; throw; }
           sink_ = nullptr;
+          for (int c = 0; c < 2; ++c) { it.sp_text[c] = (const uint8_t*)it.sp_own[c]->data(); it.sp_n[c] = it.sp_own[c]->size(); }
           it.text = it.own->data(); it.text_n = it.own->size();
         }
-      } catch (const std::exception& ex) { fail(ex.what()); it.text_n = 0; it.reads = 0; }
+      } catch (const std::exception& ex) { fail(ex.what()); it.text_n = 0; it.reads = 0; it.sp_n[0] = it.sp_n[1] = 0; }
       it.r.keep.reset();
       if (trace) it.ts[3] = now_us() - t0_us;
       if (timing) { const uint64_t tn = now_us(); us_dev += tn - ta; ts_last_dev = tn; }
       ++n_batches;
-      if (summary) {             // nothing to write: the slot is free again
+      if (!writing) {            // nothing to write: the slot is free again
         { std::lock_guard<std::mutex> lk(mu); n_objects_ += it.reads; free_slots.push_back(it.slot); }
         cv_free.notify_one();
         continue;
@@ -417,6 +447,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
         waiting.emplace(it.id, std::move(it));
         for (auto f = waiting.find(next_out); f != waiting.end(); f = waiting.find(next_out)) {   // whose turn has come
           f->second.off = out_off; out_off += f->second.text_n; n_objects_ += f->second.reads; ++next_out;
+          for (int c = 0; c < 2; ++c) { f->second.sp_off[c] = split_off[c]; split_off[c] += f->second.sp_n[c]; }
           to_write.push_back(std::move(f->second));
           waiting.erase(f);
         }
@@ -446,6 +477,14 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
         if (n <= 0) { fail("Failed to write the results file."); break; }
         done += (size_t)n;
       }
+      for (int c = 0; c < 2; ++c) {
+        if (split_fd[c] == -1) continue;
+        for (size_t sd = 0; sd < it.sp_n[c];) {
+          const ssize_t n = pwrite(split_fd[c], it.sp_text[c] + sd, it.sp_n[c] - sd, (off_t)(it.sp_off[c] + sd));
+          if (n <= 0) { fail("Failed to write " + *split_name[c] + "."); break; }
+          sd += (size_t)n;
+        }
+      }
       if (timing) { const uint64_t tn = now_us(); us_write += tn - ta; ts_last_write = tn; if (tn - ta > us_write_max) us_write_max = tn - ta; }
       if (trace) {
         it.ts[5] = now_us() - t0_us;
@@ -465,7 +504,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   std::vector<std::thread> th;
   for (size_t i = 0; i < NL; ++i) th.emplace_back(loader);
   for (size_t i = 0; i < ND; ++i) th.emplace_back(device);
-  if (!summary) {
+  if (writing) {
     for (size_t i = 1; i < NW; ++i) th.emplace_back(writer);
     writer();
   }
@@ -474,6 +513,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   const uint64_t tj1 = now_us();
   if (prealloc && ftruncate(out_fd, (off_t)out_off) != 0 && err.empty()) err = "Failed to write the results file.";
   if (out_fd != -1) close(out_fd);
+  for (int c = 0; c < 2; ++c) if (split_fd[c] != -1 && close(split_fd[c]) != 0 && err.empty()) err = "Failed to write " + *split_name[c] + ".";
   const uint64_t tj2 = now_us();
   release_batches();
   const uint64_t tj3 = now_us();

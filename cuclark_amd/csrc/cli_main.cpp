@@ -8,6 +8,7 @@
 #include <unistd.h>
 #include <string.h>
 
+#include <sys/stat.h>
 #include <sys/time.h>
 
 #include <fstream>
@@ -61,6 +62,9 @@ static void print_usage(const char* prog) {
   std::cout << "--density <file>,    also count the objects per confidence score and per gamma score (bins of 0.01, and the joint table) into <file>:\n"
                "                     CLARK's evaluate_density reports, whose cumulative columns are what --min-confidence / --min-gamma keep;\n"
                "                     works without -R like --abundance\n";
+  std::cout << "--classified-out <file>,  also write the objects that are assigned under --min-confidence / --min-gamma into <file>, as they are in -O\n";
+  std::cout << "--unclassified-out <file>,  also write the other objects (no hit, or dropped by the filter) into <file>; either option alone or both;\n"
+               "                     one -O input only (not -P, not a list of files); the names are taken as given; work without -R like --abundance\n";
   std::cout << "--min-confidence <c>, --min-gamma <g>, --highconfidence (= --min-confidence 0.75 --min-gamma 0.03), --min-abundance <a>:\n"
                "                     the filters of the abundance profile (CLARK's -c, -g, --highconfidence, -a; defaults 0.5, 0, 0)\n";
   std::cout << "--min-base-quality <Q> [--quality-offset 33|64],  FASTQ: bases of Phred quality below Q (integer in [1,93]; quality characters\n"
@@ -159,7 +163,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage, density;
+  std::string abundance, rank_report, lineage, density, classified_out, unclassified_out;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -207,6 +211,8 @@ int main(int argc, char** argv) {
     }
     if (val == "--light") { light = true; continue; }
     if (val == "--abundance") { need("Please specify the file of the abundance profile!"); abundance = argv[i]; continue; }
+    if (val == "--classified-out") { need("Please specify the file of the classified objects!"); classified_out = argv[i]; if (classified_out.empty()) { std::cerr << "Please specify the file of the classified objects!" << std::endl; exit(1); } continue; }
+    if (val == "--unclassified-out") { need("Please specify the file of the unclassified objects!"); unclassified_out = argv[i]; if (unclassified_out.empty()) { std::cerr << "Please specify the file of the unclassified objects!" << std::endl; exit(1); } continue; }
     if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
     if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
     if (val == "--lineage") {
@@ -314,11 +320,31 @@ int main(int argc, char** argv) {
   }
   if (q_offset && !min_q) { std::cerr << "--quality-offset goes with --min-base-quality <Q>." << std::endl; exit(1); }
   if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
-  if ((!abundance.empty() || !rank_report.empty() || !density.empty()) && i_results < 0 && ext) {
+  const bool split = !classified_out.empty() || !unclassified_out.empty();
+  if (split) {      // refused before any device is touched
+    // two names for one file: the same text, or the same inode when both exist
+    auto same_file = [](const std::string& a, const std::string& b) {
+      if (a.empty() || b.empty()) return false;
+      if (a == b) return true;
+      struct stat sa, sb;
+      return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+    };
+    if (i_objects2 > 0) { std::cerr << "--classified-out / --unclassified-out do not take paired-end input (-P): one -O file only." << std::endl; exit(1); }
+    if (same_file(classified_out, unclassified_out)) { std::cerr << "--classified-out and --unclassified-out name the same file: " << classified_out << std::endl; exit(1); }
+    for (const std::string* f : {&classified_out, &unclassified_out}) {
+      if (i_objects >= 0 && same_file(*f, argv[i_objects])) { std::cerr << "--classified-out / --unclassified-out would overwrite the input: " << *f << std::endl; exit(1); }
+      if (i_results >= 0 && same_file(*f, std::string(argv[i_results]) + ".csv")) { std::cerr << "--classified-out / --unclassified-out would overwrite the result CSV: " << *f << std::endl; exit(1); }
+    }
+    if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
+      std::cerr << "--classified-out / --unclassified-out do not take list-of-files mode: classify the files one at a time." << std::endl;
+      exit(1);
+    }
+  }
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || split) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty())) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && !split)) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -338,6 +364,7 @@ int main(int argc, char** argv) {
   o.abund_filter = ab_filter;
   o.rank_report = rank_report; o.lineage = lineage;
   o.density = density;
+  o.classified_out = classified_out; o.unclassified_out = unclassified_out;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   o.low_complexity = (uint32_t)lowc;
   mic::Classifier* classifier = nullptr;
@@ -361,6 +388,8 @@ int main(int argc, char** argv) {
         throw std::runtime_error("Failed to write the rank report: " + rank_report);
       std::cout << " - Rank report stored in " << rank_report << std::endl;
     }
+    if (!classified_out.empty()) std::cout << " - Classified objects stored in " << classified_out << std::endl;
+    if (!unclassified_out.empty()) std::cout << " - Unclassified objects stored in " << unclassified_out << std::endl;
     if (!density.empty()) {
       const std::vector<uint64_t> counts = classifier->density_counts();
       const std::string report = mic::density::format_report(counts.data());

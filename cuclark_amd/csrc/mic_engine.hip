@@ -174,6 +174,7 @@ struct mic_engine {
   MicAbund abund;                   // mic_abundance_*: the engine's counters (mic_abund.hip)
   MicRollup rollup;                 // mic_rollup_*: the engine's lineage and counters (mic_rollup.hip)
   MicDensity density;               // mic_density_*: the engine's counters (mic_density.hip)
+  MicSplit split;                   // mic_split_start / _stop: the engine's read-splitting setting (mic_split.hip)
 };
 
 namespace {
@@ -615,6 +616,7 @@ uint32_t* mic_engine_min_quality(mic_engine* e) { return &e->min_quality; }
 uint32_t* mic_engine_low_complexity(mic_engine* e) { return &e->low_complexity; }
 MicRollup* mic_engine_rollup(mic_engine* e) { return &e->rollup; }
 MicDensity* mic_engine_density(mic_engine* e) { return &e->density; }
+MicSplit* mic_engine_split(mic_engine* e) { return &e->split; }
 uint32_t mic_engine_row_words(const mic_engine* e) { return e->cfg.row_words; }
 hipStream_t mic_engine_stream(mic_engine* e) { return e->stream; }
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down) { *up = e->up_stream; *down = e->down_stream; }

@@ -606,3 +606,16 @@ extern "C" int mic_rollup_host(const uint32_t* rows, uint32_t row_words, const u
   }
   return MIC_OK;
 }
+
+// ---- read splitting: the rule of mic_split.h on the CPU (what stays on the host: batches handed back, the batch path, exe/split_reads,
+// tools/split_host_check.cpp): mic_split.h's partition with the rule on the result rows as its predicate.
+#include "mic_split.h"
+
+extern "C" int mic_split_host(const uint8_t* text, size_t nb, const uint64_t* rec_start, size_t n_reads, const uint32_t* results,
+                              const uint32_t* norm, int k, uint32_t n_targets, const mic_abund_filter* filter, int which, uint8_t* out,
+                              uint64_t totals[4]) {
+  if (!filter || !totals || !mic_split_which_ok(which) || (n_reads && (!text || !rec_start || !results || !out))) return MIC_E_INVALID;
+  if (!mic_abund_filter_ok(*filter) || (!norm && filter->gamma_num) || n_targets > 65535) return MIC_E_INVALID;
+  auto rule = [&](size_t r) { return mic_split_classified(results + r * MIC_RESULT_WORDS, norm ? norm[r] : 0u, k, n_targets, *filter); };
+  return mic_split_partition_host(text, nb, rec_start, n_reads, which, rule, out, totals) ? MIC_OK : MIC_E_INVALID;
+}

@@ -40,6 +40,7 @@ void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
 MicAbund* mic_engine_abund(mic_engine* e);
 MicRollup* mic_engine_rollup(mic_engine* e);
 MicDensity* mic_engine_density(mic_engine* e);
+MicSplit* mic_engine_split(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
 uint32_t* mic_engine_low_complexity(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
@@ -623,6 +624,11 @@ struct Slot {
   // u32 per read, their roll-up rows, and the pinned copy of those when the slots were allocated with want_results
   uint32_t* d_ru_rows = nullptr; uint32_t* d_rollup = nullptr; uint32_t* h_rollup = nullptr;
   uint32_t ru_row_words = 0; bool ru_valid = false;
+  // read splitting (mic_split_start on the slot's engine; allocated with the first such batch): the partition buffer and its pinned twin,
+  // max_bytes + 8 each, the work arrays of the three steps, and {a | b << 32, classified records} of the last batch in pinned memory
+  uint8_t* d_split = nullptr; uint8_t* h_split = nullptr; uint64_t* h_split_tot = nullptr;
+  MicSplitBufs split_b;
+  int split_which = 0; bool split_valid = false;
   // table-sharded batches (mic_ingest_classify_group): what this slot keeps on every engine of its group, the owner included
   struct Peer {
     mic_engine* eng = nullptr; int device = 0;
@@ -803,6 +809,33 @@ int ensure_rollup_buffers(Ingest* g, Slot& s, uint32_t rw) {
     s.host_allocs.push_back(h);
     s.h_rollup = (uint32_t*)h;
   }
+  return MIC_OK;
+}
+
+// the slot's split buffers: one device allocation and one pinned one, with the slot's first batch that is split; they go with the slot
+int ensure_split_buffers(Ingest* g, Slot& s) {
+  if (s.d_split) return MIC_OK;
+  const size_t text = (g->max_bytes + 8 + 255) & ~(size_t)255, arr = ((g->max_reads + 2) * 8 + 255) & ~(size_t)255;
+  const size_t tmp = mic_split_tmp_bytes(g->max_reads + 2);
+  void* d = nullptr; void* h = nullptr;
+  // the pinned buffer first: when it fails nothing is held, when the device allocation fails it is given back
+  mic_bind_thread_near_device(g->device, 1);
+  hipError_t e = hipHostMalloc(&h, text + 64, hipHostMallocDefault);
+  if (e == hipSuccess) memset((char*)h + text, 0, 64);
+  mic_bind_thread_near_device(g->device, 0);
+  if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu bytes of pinned memory for the split text: %s", text + 64, hipGetErrorString(e));
+  e = hipMalloc(&d, text + 2 * arr + 256 + tmp);
+  if (e != hipSuccess) {
+    hipHostFree(h);
+    return mic_set_error(MIC_E_NOMEM, "ingest slot: split buffers of %zu bytes: %s", text + 2 * arr + 256 + tmp, hipGetErrorString(e));
+  }
+  s.host_allocs.push_back(h);
+  s.dev_allocs.push_back(d);
+  char* q = (char*)d;
+  s.split_b.d_len2 = (unsigned long long*)(q + text); s.split_b.d_off2 = (unsigned long long*)(q + text + arr);
+  s.split_b.d_ncls = (uint32_t*)(q + text + 2 * arr); s.split_b.d_tmp = q + text + 2 * arr + 256; s.split_b.tmp_bytes = tmp;
+  s.h_split = (uint8_t*)h; s.h_split_tot = (uint64_t*)((char*)h + text);
+  s.d_split = (uint8_t*)d;
   return MIC_OK;
 }
 
@@ -1123,8 +1156,14 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
     std::vector<int> rcs(n_slots, MIC_OK);
     std::vector<std::string> msgs(n_slots);
     std::vector<std::thread> th;
+    // (read splitting already started on the engine: the slots' split buffers come now, pinned side by side, not with the first batches)
+    const bool split_now = mic_engine_split(e)->on;
     for (size_t i = 0; i < n_slots; ++i)
-      th.emplace_back([&, i] { rcs[i] = alloc_slot(g, g->slots[i], tmp, dev); if (rcs[i]) msgs[i] = mic_last_error(); });
+      th.emplace_back([&, i] {
+        rcs[i] = alloc_slot(g, g->slots[i], tmp, dev);
+        if (!rcs[i] && split_now) rcs[i] = ensure_split_buffers(g, g->slots[i]);
+        if (rcs[i]) msgs[i] = mic_last_error();
+      });
     for (auto& t : th) t.join();
     for (size_t i = 0; i < n_slots; ++i) {
       if (rcs[i]) return mic_set_error(rcs[i], "%s", msgs[i].c_str());
@@ -1157,6 +1196,8 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   // the base-quality threshold of the slot's engine (0: none): four-line FASTQ is then packed by pack_kernel<true>
   const uint32_t c0 = *mic_engine_min_quality(e);
   if (c0 && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while a base-quality threshold is set: the quality lines are gone");
+  const MicSplit sp = *mic_engine_split(e);
+  if (sp.on && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while read splitting is started: the quality lines are gone");
   // the low-complexity level of the slot's engine (0: none): lowc_kernel marks the masked bases, pack_kernel<*, true> skips them
   const uint32_t lc = *mic_engine_low_complexity(e);
   Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
@@ -1168,7 +1209,7 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
   ITRY(hipSetDevice(dev));
   Slot& s = g->slots[slot_id];
-  s.ru_valid = false;
+  s.ru_valid = false; s.split_valid = false;
   memset(out, 0, sizeof(*out));
   const bool resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
   const uint8_t first = resident ? (uint8_t)((flags & MIC_INGEST_RESIDENT_FASTQ) == MIC_INGEST_RESIDENT_FASTQ ? '@' : '>') : s.h_raw[0];
@@ -1295,6 +1336,26 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   if (csv_bytes > g->csv_cap || s.h_hdr[H_CONT] > g->cont_cap) status |= MIC_INGEST_TOO_MANY;
   if (status) { out->status = MIC_INGEST_FALLBACK | status; return MIC_OK; }
   s.ru_valid = roll && s.h_rollup;
+  if (sp.on) {
+    // read splitting (mic_split_start on the slot's engine, the owner of a table-sharded batch), behind the status check: class and
+    // length per record, one scan, the stable partition of the slot's text; then the classes asked for go to the slot's pinned buffer
+    if ((rc = ensure_split_buffers(g, s))) return rc;
+    ITRY(mic_launch_split(s.d_raw, nb, s.rec.name_s, 1u, s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, sp.filter, sp.which,
+                          s.split_b, s.d_split, nullptr, st));
+    ITRY(hipMemcpyAsync(s.h_split_tot, s.split_b.d_off2 + n_reads, 8, hipMemcpyDeviceToHost, st));
+    ITRY(hipMemcpyAsync(s.h_split_tot + 1, s.split_b.d_ncls, 4, hipMemcpyDeviceToHost, st));
+    ITRY(hipEventRecord(s.ev, st));
+    ITRY(wait_event(s.ev));
+    const uint64_t a = (uint32_t)s.h_split_tot[0], b = s.h_split_tot[0] >> 32;
+    if (a + b > (uint64_t)nb + 1) return mic_set_error(MIC_E_STATE, "split: %llu + %llu bytes from a text of %u", (unsigned long long)a, (unsigned long long)b, nb);
+    const uint64_t lo = (sp.which & MIC_SPLIT_CLASSIFIED) ? 0 : a, hi = (sp.which & MIC_SPLIT_UNCLASSIFIED) ? a + b : a;
+    if (hi > lo) ITRY(hipMemcpyAsync(s.h_split + lo, s.d_split + lo, hi - lo, hipMemcpyDeviceToHost, down));   // (the partition is complete: the wait above)
+    if (no_csv) {      // (with a CSV, phase 3's wait for the download stream covers this copy)
+      ITRY(hipEventRecord(s.ev, down));
+      ITRY(wait_event(s.ev));
+    }
+    s.split_which = sp.which; s.split_valid = true;
+  }
   if (no_csv) {
     out->n_reads = n_reads; out->csv_bytes = 0; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
     out->status = MIC_INGEST_OK;
@@ -1342,6 +1403,24 @@ int mic_ingest_rollup_rows(mic_engine* e, size_t slot_id, const uint32_t** rollu
   const Slot& s = g->slots[slot_id];
   if (!s.ru_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no roll-up rows (mic_rollup_start, want_results, MIC_INGEST_OK)");
   *rollup = s.h_rollup; *n_reads = s.n_reads;
+  return MIC_OK;
+}
+
+int mic_ingest_split_text(mic_engine* e, size_t slot_id, const uint8_t** classified, uint64_t* classified_bytes, uint64_t* n_classified,
+                          const uint8_t** unclassified, uint64_t* unclassified_bytes, uint64_t* n_unclassified) {
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
+  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  const Slot& s = g->slots[slot_id];
+  if (!s.split_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no split text (mic_split_start, MIC_INGEST_OK)");
+  const uint64_t a = (uint32_t)s.h_split_tot[0], b = s.h_split_tot[0] >> 32, nc = s.h_split_tot[1];
+  const bool wc = (s.split_which & MIC_SPLIT_CLASSIFIED) != 0, wu = (s.split_which & MIC_SPLIT_UNCLASSIFIED) != 0;
+  if (classified) *classified = wc ? s.h_split : nullptr;
+  if (classified_bytes) *classified_bytes = wc ? a : 0;
+  if (n_classified) *n_classified = nc;
+  if (unclassified) *unclassified = wu ? s.h_split + a : nullptr;
+  if (unclassified_bytes) *unclassified_bytes = wu ? b : 0;
+  if (n_unclassified) *n_unclassified = s.n_reads - nc;
   return MIC_OK;
 }
 

@@ -240,6 +240,26 @@ struct MicDensity {
 hipError_t mic_launch_density(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
                               int n_cu, unsigned long long* counts, const uint32_t* status, hipStream_t s);
 
+// ---- read splitting (mic_split.hip; the rule: mic_split.h) --------------------------------------------------------------------------
+// An engine's setting while mic_split_start is in force: every ingest batch it owns that returns MIC_INGEST_OK is partitioned.
+struct MicSplit {
+  bool on = false;
+  int which = 0;                    // MIC_SPLIT_CLASSIFIED | MIC_SPLIT_UNCLASSIFIED
+  mic_abund_filter filter = {5, 10, 0, 1};
+};
+// work arrays of one launch: n + 1 u64 each (scan input and output), one u32 counter, the scan's temporary storage
+struct MicSplitBufs {
+  unsigned long long* d_len2 = nullptr; unsigned long long* d_off2 = nullptr; uint32_t* d_ncls = nullptr;
+  void* d_tmp = nullptr; size_t tmp_bytes = 0;
+};
+size_t mic_split_tmp_bytes(size_t n_items);
+// partitions the n records of text[0, nb) into out[0, nb + 1): record r begins at starts[r] - start_sub (the last one ends at nb), its
+// class comes from results / norm / norm_sub as in mic_launch_abund.  Afterwards b.d_off2[n] = a | b << 32 and *b.d_ncls = the number
+// of classified records.  text and out 4-byte aligned; status as for mic_launch_abund.
+hipError_t mic_launch_split(const uint8_t* text, uint32_t nb, const uint32_t* starts, uint32_t start_sub, const uint32_t* results,
+                            const uint32_t* norm, uint32_t norm_sub, uint32_t n, int k, uint32_t n_targets, const mic_abund_filter& f,
+                            int which, const MicSplitBufs& b, uint8_t* out, const uint32_t* status, hipStream_t s);
+
 // ---- rank roll-up (mic_rollup.hip; the rule: mic_rollup.h) ------------------------------------------------------------------------
 // An engine's lineage (mic_rollup_set) and, while mic_rollup_start is in force, its counters.  The lineage's device arrays are one
 // allocation (d_block).

@@ -446,6 +446,35 @@ class MiClarkDB:
         check(self.L.mic_ingest_rollup_rows(self.h, slot, C.byref(p), C.byref(n)))
         return _as_np(p.value, (int(n.value), _lib.MIC_ROLLUP_WORDS), np.uint32).copy()
 
+    # -- read splitting (mic_split_*): the classified / unclassified records of a batch, partitioned on the device (csrc/mic_split.h)
+    def split_start(self, filt=None, which=3):
+        """From now on every ingest batch of this engine that returns MIC_INGEST_OK is split: which = 1 classified, 2 unclassified, 3 both."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_split_start(self.h, C.byref(f), int(which)))
+
+    def split_stop(self):
+        check(self.L.mic_split_stop(self.h))
+
+    def ingest_split_text(self, slot):
+        """dict(classified, unclassified (bytes, or None when the class was not asked for), n_classified, n_unclassified) of the slot's
+        last batch; MicError (MIC_E_STATE) when it left none."""
+        pc, pu = C.c_void_p(0), C.c_void_p(0)
+        bc, bu, nc, nu = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.L.mic_ingest_split_text(self.h, slot, C.byref(pc), C.byref(bc), C.byref(nc), C.byref(pu), C.byref(bu), C.byref(nu)))
+        return dict(classified=C.string_at(pc.value, bc.value) if pc.value else None,
+                    unclassified=C.string_at(pu.value, bu.value) if pu.value else None,
+                    n_classified=int(nc.value), n_unclassified=int(nu.value))
+
+    def split_device(self, d_text, nb, d_rec_start, n_reads, d_results, d_norm, d_out, filt=None, which=3, stream=0):
+        """The kernels alone on caller-owned device memory; returns (a, b, n_classified, n_unclassified).  Synchronous."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        tot = np.zeros(4, np.uint64)
+        check(self.L.mic_split_device(self.h, d_text, nb, d_rec_start, n_reads, d_results, d_norm or None, C.byref(f), int(which), d_out,
+                                      tot.ctypes.data, stream or None))
+        return tuple(int(x) for x in tot)
+
     def ingest_fetch_group_rows(self, slot, part):
         """test hook: the partial rows engine `part` of the group computed for the slot's last table-sharded batch"""
         n, rw = C.c_uint64(0), C.c_uint32(0)

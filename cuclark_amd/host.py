@@ -147,6 +147,26 @@ def abundance_host(results, norm, k, n_targets, filt=None):
     return counts
 
 
+def split_host(data, rec_start, results, norm, k, n_targets, filt=None, which=3):
+    """mic_split_host: the text's records (rec_start: u64 byte offsets, [0] = 0) partitioned by the rule of csrc/mic_split.h.
+    Returns (out u8[len(data) + 1], (a, b, n_classified, n_unclassified)): classified records at out[:a], unclassified at
+    out[a:a + b]; a class `which` (1 classified, 2 unclassified, 3 both) does not name is not written."""
+    L = _lib.load()
+    buf = np.frombuffer(data, np.uint8)
+    results = np.ascontiguousarray(results, np.uint32).reshape(-1, 8)
+    starts = np.ascontiguousarray(rec_start, np.uint64)
+    nm = np.ascontiguousarray(norm, np.uint32) if norm is not None else None
+    out = np.full(buf.size + 1, 0xA5, np.uint8)
+    tot = np.zeros(4, np.uint64)
+    f = filt if filt is not None else abund_filter()
+    rc = L.mic_split_host(buf.ctypes.data, buf.size, starts.ctypes.data, starts.size, results.ctypes.data,
+                          nm.ctypes.data if nm is not None else None, int(k), int(n_targets), C.byref(f), int(which), out.ctypes.data,
+                          tot.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_split_host: invalid argument ({rc})")
+    return out, tuple(int(x) for x in tot)
+
+
 def density_host(results, norm, k, n_targets, counts=None):
     """mic_density_host: u64[5153] score-density counters of the result rows (u32[n, 8]) by the rule of csrc/mic_density.h
     ([0] reads, [1] unassigned, [2 + (c - 50) * 101 + g]).  norm: the CSV's Length column per read, or None (gamma bin 0).

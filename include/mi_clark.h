@@ -573,6 +573,43 @@ int mic_density_device(mic_engine* e, const uint32_t* d_results, const uint32_t*
 int mic_density_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets, uint64_t* counts);
 long mic_density_format(const uint64_t* counts, size_t n, int which, char* buf, size_t cap);
 
+/* ---- read splitting: the classified and the unclassified reads themselves, partitioned on the device (csrc/mic_split.h: the rule) ----
+ * The reference says what every read is and cannot hand the reads back.  Record r of a text is the bytes from the first byte of its
+ * header line up to the first byte of the next record's header line (the last record: to the end of the text); records are those of
+ * the library's indexers and tile the text.  A record is CLASSIFIED iff it counts for a target under the abundance filter (bucket >= 2
+ * of mic_abundance_*: norm and filter exactly as there), UNCLASSIFIED otherwise.  Each class's records are concatenated in input order,
+ * byte for byte ('\r', wrapped lines, '+' and quality lines, trailing blank lines of the last record); a text whose last byte is not
+ * '\n' gets one '\n' appended to its last record - the only byte ever added.  The masks (mic_ingest_set_min_quality /
+ * _low_complexity) change which class a record falls into, never its bytes.
+ *   partition buffer  nb + 1 bytes: classified records at [0, a), unclassified records at [a, a + b), a + b = nb or nb + 1.  A class
+ *                     that `which` does not name is not copied: its part of the buffer is left as it was.
+ *   totals            u64[4] = {a, b, classified records, unclassified records}
+ * mic_split_start / _stop  engine state, next to mic_abundance_start: from then on every mic_ingest_classify / _group batch owned by
+ *                        this engine that returns MIC_INGEST_OK is partitioned behind the query, on the slot's stream, and the text of
+ *                        the classes asked for is brought to a pinned buffer of the slot (allocated, with its device twin, by
+ *                        mic_ingest_alloc when the split is started by then, else with the slot's first such batch); with and without MIC_INGEST_NO_CSV; a batch handed back (MIC_INGEST_FALLBACK)
+ *                        produces nothing and the caller splits it with mic_split_host.  MIC_INGEST_FASTQ_2LINE while started:
+ *                        MIC_E_INVALID (the quality lines are gone).  In a table-sharded group the owner splits, from the group's final
+ *                        results.  A filter that fails the test of mic_abundance_start: MIC_E_INVALID.
+ * mic_ingest_split_text  the split of the slot's last batch: pointers into the slot's pinned buffer, valid until the slot's next call
+ *                        (a class that was not asked for: NULL and 0 bytes; its record count is still given); MIC_E_STATE when the
+ *                        slot's last batch left none.  Any out pointer may be NULL.
+ * mic_split_device       the kernels alone on caller-owned device memory: d_text (nb bytes, 1 B .. 128 MiB, 4-byte aligned),
+ *                        d_rec_start (u32 per record, ascending, [0] = 0), d_results, d_norm (NULL: only a filter without gamma),
+ *                        d_out (nb + 1 bytes, 4-byte aligned).  Synchronous on `stream` (NULL = the engine's stream).
+ * mic_split_host         the rule on the CPU, no device needed: rec_start as u64 (mic_index_reads: name_s - 1), `out` of nb + 1 bytes.
+ *                        MIC_E_INVALID when the starts do not begin at 0, do not ascend or reach nb. */
+#define MIC_SPLIT_CLASSIFIED 1
+#define MIC_SPLIT_UNCLASSIFIED 2
+int mic_split_start(mic_engine* e, const mic_abund_filter* filter, int which);
+int mic_split_stop(mic_engine* e);
+int mic_ingest_split_text(mic_engine* e, size_t slot, const uint8_t** classified, uint64_t* classified_bytes, uint64_t* n_classified,
+                          const uint8_t** unclassified, uint64_t* unclassified_bytes, uint64_t* n_unclassified);
+int mic_split_device(mic_engine* e, const uint8_t* d_text, size_t nb, const uint32_t* d_rec_start, size_t n_reads, const uint32_t* d_results,
+                     const uint32_t* d_norm, const mic_abund_filter* filter, int which, uint8_t* d_out, uint64_t totals[4], void* stream);
+int mic_split_host(const uint8_t* text, size_t nb, const uint64_t* rec_start, size_t n_reads, const uint32_t* results, const uint32_t* norm,
+                   int k, uint32_t n_targets, const mic_abund_filter* filter, int which, uint8_t* out, uint64_t totals[4]);
+
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */
 int mic_format_ratio_g(uint32_t num, uint32_t den, char* out16);

@@ -211,6 +211,10 @@ int mic_rollup_set(mic_engine*, uint32_t, const uint16_t*) { return MIC_OK; }
 int mic_rollup_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
 int mic_rollup_fetch(mic_engine*, uint64_t* counts, size_t n) { for (size_t i = 0; i < n; ++i) counts[i] = 0; return MIC_OK; }
 int mic_rollup_stop(mic_engine*) { return MIC_OK; }
+// read splitting: the mock partitions nothing on its "device" (mic_split_host is mic_host.cpp's and under test)
+int mic_split_start(mic_engine*, const mic_abund_filter*, int) { return MIC_OK; }
+int mic_split_stop(mic_engine*) { return MIC_OK; }
+int mic_ingest_split_text(mic_engine*, size_t, const uint8_t**, uint64_t*, uint64_t*, const uint8_t**, uint64_t*, uint64_t*) { return MIC_E_STATE; }
 }  // extern "C"
 
 namespace {
