@@ -132,11 +132,31 @@ __device__ __forceinline__ uint32_t s_torder(uint64_t tv) {
   return h;
 }
 __device__ __forceinline__ uint32_t s_torder24(uint32_t tv) { return __umul24(tv, 0x9E3779u) + 0x27D4EB2Fu; }   // tv < 2^24
+// Pair swap and complement of a word of bit-reversed nucleotides, the two shifted copies given: even bits = ~a, odd bits = ~b with
+// a = r >> 1, b = r << 1.  Both masks, the merge and the complement are ONE three-input boolean (v_bitop3_b32, truth table 0x1B over
+// a, b, 0x55555555); the compiler does not find it by itself - written out it keeps a v_and in front (shift, shift, and, bitop3).
+__device__ __forceinline__ uint32_t swap_comp_pairs(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, 0x55555555u, 0x1B);
+#else
+  return ~((a & 0x55555555u) | (b & ~0x55555555u));
+#endif
+}
 // reverse complement of a t-mer of at most 16 nucleotides
 __device__ __forceinline__ uint32_t revcomp_bits32(uint32_t x, int t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // r >> 1 and r << 1 of r = bitreverse(x) >> (32 - 2t) straight from the reversed word.  r << 1 is the reversed word shifted by
+  // 31 - 2t: the bit that comes in at the bottom sits on an even position, where a is taken, and the one on top is masked off -
+  // bfrev, two shifts, bitop3 and the mask, 5 VALU for t = 8 instead of 7.  A t known only at run time (the generic kernels) may be
+  // 16, where that shift count would be -1: there the left shift goes first, one instruction more and still one fewer than before.
+  const uint32_t br = __builtin_bitreverse32(x);
+  const uint32_t b = (__builtin_constant_p(t) && t < 16) ? br >> (31 - 2 * t) : (br << 1) >> (32 - 2 * t);
+  return swap_comp_pairs(br >> (33 - 2 * t), b) & (t >= 16 ? 0xFFFFFFFFu : (1u << (2 * t)) - 1u);
+#else
   uint32_t r = __builtin_bitreverse32(x) >> (32 - 2 * t);
   r = ((r >> 1) & 0x55555555u) | ((r << 1) & ~0x55555555u);
   return ~r & (t >= 16 ? 0xFFFFFFFFu : (1u << (2 * t)) - 1u);
+#endif
 }
 // sequential form: f(p) for every position p (0 .. w-1) the query may sample for the k-mer K as it reads (every tie)
 template <typename F>

@@ -420,6 +420,10 @@ __device__ __forceinline__ uint32_t row_suffix_min(uint32_t t) {
   x = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)t, 0x102, 0xF, 0xF, false); t = x < t ? x : t;
   x = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)t, 0x104, 0xF, 0xF, false); t = x < t ? x : t;
   x = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)t, 0x108, 0xF, 0xF, false); t = x < t ? x : t;
+  // (the result opaque: the caller's next minimum would otherwise be fused with this step's into one v_min3_u32, which takes no DPP
+  // operand - a v_mov -1 for the lanes without a source and a v_mov_dpp in front of it, three instructions where v_min_u32_dpp and
+  // v_min_u32 are two.  Not volatile: a suffix minimum nobody reads still goes away.)
+  asm("" : "+v"(t));
   return t;
 }
 
@@ -1331,12 +1335,21 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     if (!FWD) {
       const uint32_t sh = 96u - 2u * (uint32_t)(k + ctx);
       const uint32_t r0 = __builtin_bitreverse32(G2), r1 = __builtin_bitreverse32(G1), r2 = __builtin_bitreverse32(G0);
-      uint32_t q0 = sh ? __builtin_amdgcn_alignbit(r0, r1, 32u - sh) : r0;
-      uint32_t q1 = sh ? __builtin_amdgcn_alignbit(r1, r2, 32u - sh) : r1;
-      uint32_t q2 = r2 << sh;
-      q0 = ~(((q0 >> 1) & 0x55555555u) | ((q0 << 1) & 0xAAAAAAAAu));
-      q1 = ~(((q1 >> 1) & 0x55555555u) | ((q1 << 1) & 0xAAAAAAAAu));
-      q2 = ~(((q2 >> 1) & 0x55555555u) | ((q2 << 1) & 0xAAAAAAAAu));
+      // the reversed words realigned by sh (even, 0 .. 30), then pair swap and complement = swap_comp_pairs(q >> 1, q << 1).  With k and
+      // m as constants the two shifted copies come straight out of the funnel shift by sh -+ 1: the bit each of them has too many sits
+      // where the other copy is taken (top bit of q >> 1: an odd position; bottom bit of q << 1: an even one) - two funnel shifts
+      // and one bitop3 per word.  (With sh known only at run time the case sh = 0 would cost a second select per word.)
+      uint32_t q0, q1, q2;
+      if (KK != 0 && sh != 0) {
+        q0 = swap_comp_pairs(__builtin_amdgcn_alignbit(r0, r1, 33u - sh), __builtin_amdgcn_alignbit(r0, r1, 31u - sh));
+        q1 = swap_comp_pairs(__builtin_amdgcn_alignbit(r1, r2, 33u - sh), __builtin_amdgcn_alignbit(r1, r2, 31u - sh));
+        q2 = swap_comp_pairs(r2 << (sh - 1u), r2 << (sh + 1u));
+      } else {
+        q0 = sh ? __builtin_amdgcn_alignbit(r0, r1, 32u - sh) : r0;
+        q1 = sh ? __builtin_amdgcn_alignbit(r1, r2, 32u - sh) : r1;
+        q2 = r2 << sh;
+        q0 = swap_comp_pairs(q0 >> 1, q0 << 1); q1 = swap_comp_pairs(q1 >> 1, q1 << 1); q2 = swap_comp_pairs(q2 >> 1, q2 << 1);
+      }
       uint32_t kr, hr;
       region_x(q0, q1, kr, hr);
       rev = hr < xhi || (hr == xhi && kr < key);
