@@ -158,6 +158,7 @@ __device__ __forceinline__ uint32_t revcomp_bits32(uint32_t x, int t) {
   return ~r & (t >= 16 ? 0xFFFFFFFFu : (1u << (2 * t)) - 1u);
 #endif
 }
+#include "mic_front3.h"     // k = 31, m = 20: the query's front half with three t-mers per lane, and its host model
 // sequential form: f(p) for every position p (0 .. w-1) the query may sample for the k-mer K as it reads (every tie)
 template <typename F>
 __device__ __forceinline__ void s_sampled(uint64_t K, int k, int m, bool canon, F&& f) {

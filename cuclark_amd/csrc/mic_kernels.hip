@@ -534,6 +534,59 @@ __device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_
   qa0 = (uint32_t)lane_inv + d0; qa1 = 64u + (uint32_t)lane_inv + d1;
 }
 
+// The same for k = 31, m = 20 with THREE t-mers per lane (round 8; mic_front3.h has the layout, the arithmetic and the host model):
+// t = 8, W = 24 = 8 x 3, lane a owns the t-mers and the k-mers at chunk positions 3a, 3a+1, 3a+2.  The 143 t-mers of a 150-bp read
+// are one array of 48 lanes instead of three of 64 with 15 lanes in the third; the sliding minimum is nine v_min / v_min3 and five
+// ds_bpermute (two rows of DPP scans per array, broadcasts and first-row fix-ups before), the three t-mers come out of ONE funnel
+// shift of two window dwords (2 ds_bpermute instead of 6) and their reverse complements out of one reverse complement of the ten
+// nucleotides they span.  Keys, windows and ties are what sampled_positions computes: every k-mer takes the minimum over the same 24
+// keys, so nothing is masked here either - what lies past the part reaches only k-mers past n_act, which leave as ~0.
+// Registers: the kernel runs at its budget of 64 and this form fills it without spilling.  What keeps it there: the position bits
+// are inserted by one v_bitop3 from the position itself (no register of pre-masked bits per element), the sentinel of the k-mers
+// past n_act is an inline constant, and the positions are computed on 3 lane and its negative (the first form kept all of these
+// resident next to the five fetch addresses: 8 bytes of scratch in the two-strand instantiations).
+// s0 .. s2: chunk position of the sampled m-mer of k-mers 3 lane + 0 .. 2 (below 256 whatever the lane holds); q0 .. q2: the same, or
+// ~0 - an inline constant - for the k-mers past n_act; p0: 3 lane.
+template <bool CANON>
+__device__ __forceinline__ void sampled_positions3(uint32_t wd, int lane_inv, uint32_t n_act, uint32_t& p0, uint32_t& s0, uint32_t& s1, uint32_t& s2,
+                                                    uint32_t& q0, uint32_t& q1, uint32_t& q2) {
+  const int at = lane_inv << 2;
+  const int ad = f3_dword(lane_inv) << 2;
+  const uint32_t tsh = f3_shift(lane_inv);
+  p0 = 3u * (uint32_t)lane_inv;
+  const uint32_t np0 = 0u - p0;
+  const uint32_t W0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad, (int)wd), W1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad + 4, (int)wd);
+  const uint32_t X = __builtin_amdgcn_alignbit(W0, W1, tsh);
+  uint32_t t0 = f3_tmer(X, 0), t1 = f3_tmer(X, 1), t2 = f3_tmer(X, 2);
+  if (CANON) {
+    // bitreverse(X): the ten nucleotides in reversed order in bits 0 .. 19, the bits of every pair swapped; what sits above is not read
+    const uint32_t br = __builtin_bitreverse32(X);
+    const uint32_t Y = swap_comp_pairs(br >> 1, br << 1);
+    t0 = f3_min(t0, f3_tmer_rc(Y, 0)); t1 = f3_min(t1, f3_tmer_rc(Y, 1)); t2 = f3_min(t2, f3_tmer_rc(Y, 2));
+  }
+  // (h & ~31) | (pos & 31) = f3_key: bits of pos where the constant 31 has them, of h elsewhere (truth table 0xD8 over h, pos, 31)
+  auto key = [](uint32_t tv, uint32_t pos) { return (uint32_t)__builtin_amdgcn_bitop3_b32(s_torder24(tv), pos, 31u, 0xD8); };
+  const uint32_t k0 = key(t0, p0), k1 = key(t1, p0 + 1u), k2 = key(t2, p0 + 2u);
+  const uint32_t T = f3_min3(k0, k1, k2), e12 = f3_min(k1, k2), e01 = f3_min(k0, k1);
+  // (ds_bpermute wraps the lane number by itself)
+  const uint32_t x1 = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 4, (int)T);
+  const uint32_t m2 = f3_min(T, x1);
+  const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 8, (int)m2);
+  const uint32_t m4 = f3_min(m2, y);
+  const uint32_t z = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 16, (int)m4);
+  const uint32_t k0n = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 32, (int)k0), e01n = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 32, (int)e01);
+  uint32_t r0, r1, r2;
+  f3_combine(k2, e12, m4, x1, y, z, k0n, e01n, r0, r1, r2);
+  // f3_sampled of r and 3 lane + j, written on 3 lane and its negative
+  auto sampled = [&](uint32_t r, uint32_t j) {
+    const uint32_t d = (r + np0 - j) & 31u, e = d - (uint32_t)F3_WM;
+    return f3_min(d, e) + p0 + j;
+  };
+  const int nv = (int)(n_act + np0);               // k-mers of the chunk from 3 lane on
+  s0 = sampled(r0, 0u); s1 = sampled(r1, 1u); s2 = sampled(r2, 2u);
+  q0 = nv > 0 ? s0 : ~0u; q1 = nv > 1 ? s1 : ~0u; q2 = nv > 2 ? s2 : ~0u;
+}
+
 #ifndef MIC_SPEC
 #define MIC_SPEC 1
 #endif
@@ -1282,6 +1335,28 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
                                   : window_word_w(cont, first, cend, base, ln, false, 0u);
     wd_out = wd;
     const uint32_t n_act = nk - base < 128u ? nk - base : 128u;
+    if constexpr (KK == F3_K && MM == F3_M) {
+      // three k-mers per lane (sampled_positions3): element 0 of a lane follows element 2 of the lane below; k-mer n_act - it always
+      // exists, 3 x 64 > 128 - counts as ~0 and leads the closing record (only the k-mer of a closing record is ever read: its low
+      // byte is whatever the lane computed)
+      uint32_t p0, s0, s1, s2, q0, q1, q2;
+      sampled_positions3<!FWD>(wd, lane, n_act, p0, s0, s1, s2, q0, q1, q2);
+      const uint32_t pv = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)q2, 0x138, 0xF, 0xF, false);
+      const bool f0 = q0 != pv, f1 = q1 != q0, f2 = q2 != q1;
+      const uint64_t b0 = wballot(f0), b1 = wballot(f1), b2 = wballot(f2);
+      const uint32_t R = __popcll(b0) + __popcll(b1) + __popcll(b2) - 1u;
+      uint32_t c = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u));
+      c = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, c));
+      c = __builtin_amdgcn_mbcnt_hi((uint32_t)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b2, c));
+      __builtin_amdgcn_wave_barrier();
+      // f3_rank: the lane's own earlier leaders on top (one add with carry each)
+      const uint32_t c1 = c + (f0 ? 1u : 0u), c2 = c1 + (f1 ? 1u : 0u);
+      if (f0) rec[c] = f3_record(s0, p0);
+      if (f1) rec[c1] = f3_record(s1, p0 + 1u);
+      if (f2) rec[c2] = f3_record(s2, p0 + 2u);
+      __builtin_amdgcn_wave_barrier();
+      return R;
+    }
     const bool past = n_act + (uint32_t)(k - s_tlen(k, m)) >= 129u;
     uint32_t qa0, qa1;
     sampled_positions<!FWD>(wd, ln, lane, k, m, past, qa0, qa1);
