@@ -20,6 +20,7 @@ MIC_ROW_INVALID = 0xFFFFFFFF
 MIC_ROLLUP_WORDS, MIC_ROLLUP_MAX_LEVELS = 8, 7
 MIC_ROLLUP_UNRESOLVED, MIC_ROLLUP_PENDING = 0xFFFFFFFF, 0xFFFFFFFE
 MIC_DENSITY_WORDS, MIC_DENSITY_CONF_BINS, MIC_DENSITY_GAMMA_BINS = 5153, 51, 101
+MIC_KSKETCH_REGS = 16384
 MIC_LAYOUT_AUTO, MIC_LAYOUT_DIRECT, MIC_LAYOUT_MINIMIZER, MIC_LAYOUT_SUPER, MIC_LAYOUT_SUPER2 = 0, 1, 2, 3, 4
 
 
@@ -162,6 +163,14 @@ SYMBOLS = [
     ("mic_density_device", C.c_int, [_VP, _VP, _VP, _SZ, _VP, _VP]),
     ("mic_density_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, _VP]),
     ("mic_density_format", C.c_long, [_VP, _SZ, C.c_int, C.c_char_p, _SZ]),
+    ("mic_ksketch_device", C.c_int, [_VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP]),
+    ("mic_ksketch_start", C.c_int, [_VP]),
+    ("mic_ksketch_fetch", C.c_int, [_VP, _VP, _SZ, _VP, _SZ]),
+    ("mic_ksketch_stop", C.c_int, [_VP]),
+    ("mic_batch_ksketch", C.c_int, [_VP, _SZ]),
+    ("mic_ksketch_add_host", C.c_int, [_VP, _VP, _SZ, C.c_int, C.c_uint32, _VP, _VP]),
+    ("mic_ksketch_estimate", C.c_double, [_VP]),
+    ("mic_ksketch_format", C.c_long, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_char_p, _SZ]),
     ("mic_split_start", C.c_int, [_VP, C.POINTER(MicAbundFilter), C.c_int]),
     ("mic_split_stop", C.c_int, [_VP]),
     ("mic_ingest_split_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_VP),

@@ -268,6 +268,7 @@ void Classifier::reset_counts() {
     std::lock_guard<std::mutex> lk(count_mu_);
     host_density_.assign(MIC_DENSITY_WORDS, 0);
   }
+  if (sketching()) for (mic_engine* e : engines_) check(mic_ksketch_start(e), "k-mer sketches");
   if (!counting()) return;
   for (mic_engine* e : engines_) check(mic_abundance_start(e, &opt_.abund_filter), "abundance counters");
   std::lock_guard<std::mutex> lk(count_mu_);
@@ -312,6 +313,18 @@ std::vector<uint64_t> Classifier::density_counts() {
   std::lock_guard<std::mutex> lk(count_mu_);
   for (size_t i = 0; i < host_density_.size() && i < total.size(); ++i) total[i] += host_density_[i];
   return total;
+}
+
+void Classifier::ksketch_result(std::vector<uint8_t>& regs, std::vector<uint64_t>& hits) {
+  const size_t T = names_.size();
+  regs.assign(T * MIC_KSKETCH_REGS, 0); hits.assign(T, 0);
+  std::vector<uint8_t> r(regs.size());
+  std::vector<uint64_t> h(T);
+  for (mic_engine* e : engines_) {
+    check(mic_ksketch_fetch(e, r.data(), r.size(), h.data(), h.size()), "k-mer sketches");
+    for (size_t i = 0; i < r.size(); ++i) if (r[i] > regs[i]) regs[i] = r[i];
+    for (size_t i = 0; i < T; ++i) hits[i] += h[i];
+  }
 }
 
 std::vector<uint64_t> Classifier::rollup_counts() {
@@ -473,6 +486,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
     return;
   }
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
+  if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");
@@ -555,6 +569,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
     list_mode = !((!line.empty() && (line[0] == '>' || line[0] == '@')) || ele.size() == 2);
   }
   if (!list_mode) { one(f1, f2, results, false); return; }
+  if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");

@@ -37,6 +37,7 @@ struct Options {
   mic_abund_filter abund_filter = {5, 10, 0, 1};             // --min-confidence / --min-gamma / --highconfidence (CLARK's -c 0.5 -g 0)
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
   std::string density;                                       // --density <file>: the score densities are counted (mic_density_*)
+  std::string kmer_report;                                   // --kmer-report <file>: distinct k-mers hit per target are sketched (mic_ksketch_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
   std::string classified_out, unclassified_out;              // --classified-out / --unclassified-out <file>: the reads themselves, split (mic_split_*)
   uint32_t low_complexity = 0;                               // --mask-low-complexity <level>: DUST level in [1,149], 0 = off (mic_lowc.h)
@@ -96,6 +97,8 @@ class Classifier {
   std::vector<uint64_t> rollup_counts();
   // --density: the MIC_DENSITY_WORDS counters of the run (csrc/mic_density.h), summed the same way
   std::vector<uint64_t> density_counts();
+  // --kmer-report: the run's sketches (csrc/mic_ksketch.h), the engines' merged: registers by max, hits by sum
+  void ksketch_result(std::vector<uint8_t>& regs, std::vector<uint64_t>& hits);
   const rank::Lineage& lineage() const { return lineage_; }
 
   // --classified-out / --unclassified-out: is `objects` with `results` a list-of-files run?  (no device needed: asked before one is touched)
@@ -130,7 +133,9 @@ class Classifier {
   bool gz_on_device_ = true;                  // compressed input is inflated on the first engine's device (needs peer access from the others)
   std::atomic<size_t> n_objects_{0};
   // --abundance: every run over the input starts the counters afresh (a run the feeder gives up is repeated from the start)
-  bool counting() const { return !opt_.abundance.empty(); }
+  // (--kmer-report prints the reads --abundance gives every target: it starts the same counters)
+  bool counting() const { return !opt_.abundance.empty() || sketching(); }
+  bool sketching() const { return !opt_.kmer_report.empty(); }
   bool ranking() const { return !opt_.rank_report.empty(); }
   bool densing() const { return !opt_.density.empty(); }
   // --classified-out / --unclassified-out: the classes asked for (0: none).  The streaming path takes the split text from the engines

@@ -202,6 +202,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
         check(mic_batch_ready(engines_[d], lb, cnt, m), "readyBatch");
         check(mic_batch_query(engines_[d], lb, (opt_.extended || ranking()) ? 1 : 0, 0), "queryBatch");
         check(mic_batch_wait(engines_[d], lb), "waitForBatch");
+        if (sketching()) check(mic_batch_ksketch(engines_[d], lb), "k-mer sketches");      // (the batch's packed reads and results are still on the device)
       } else {
         // every engine of the group probes the same reads against its part of the table - one upload into the first engine, the packed
         // reads fanned out device to device (mic_batch_query_group; the reference uploads the host arrays to every device,

@@ -19,6 +19,7 @@
 #include "abundance_table.hpp"
 #include "classifier.hpp"
 #include "density_report.hpp"
+#include "kmer_report.hpp"
 #include "mic_abund.h"
 
 #define MAXK 32
@@ -61,6 +62,10 @@ static void print_usage(const char* prog) {
                "                     (label<TAB>name_1<TAB>...<TAB>name_L per target) or from <DB>/../taxonomy; works without -R like --abundance\n";
   std::cout << "--density <file>,    also count the objects per confidence score and per gamma score (bins of 0.01, and the joint table) into <file>:\n"
                "                     CLARK's evaluate_density reports, whose cumulative columns are what --min-confidence / --min-gamma keep;\n"
+               "                     works without -R like --abundance\n";
+  std::cout << "--kmer-report <file>, also sketch the distinct k-mers the objects hit in every target (HyperLogLog, 16384 registers per target) into\n"
+               "                     <file>: Name,Reads,Kmers,DistinctKmers,Duplication - many reads over few distinct k-mers (a high duplication) mark\n"
+               "                     a low-complexity or contamination artefact; Reads as in --abundance; not with --db-sharded or a list of files;\n"
                "                     works without -R like --abundance\n";
   std::cout << "--classified-out <file>,  also write the objects that are assigned under --min-confidence / --min-gamma into <file>, as they are in -O\n";
   std::cout << "--unclassified-out <file>,  also write the other objects (no hit, or dropped by the filter) into <file>; either option alone or both;\n"
@@ -163,7 +168,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage, density, classified_out, unclassified_out;
+  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -214,6 +219,7 @@ int main(int argc, char** argv) {
     if (val == "--classified-out") { need("Please specify the file of the classified objects!"); classified_out = argv[i]; if (classified_out.empty()) { std::cerr << "Please specify the file of the classified objects!" << std::endl; exit(1); } continue; }
     if (val == "--unclassified-out") { need("Please specify the file of the unclassified objects!"); unclassified_out = argv[i]; if (unclassified_out.empty()) { std::cerr << "Please specify the file of the unclassified objects!" << std::endl; exit(1); } continue; }
     if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
+    if (val == "--kmer-report") { need("Please specify the file of the k-mer report!"); kmer_report = argv[i]; if (kmer_report.empty()) { std::cerr << "Please specify the file of the k-mer report!" << std::endl; exit(1); } continue; }
     if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
     if (val == "--lineage") {
       need("Please specify the lineage file!");
@@ -321,14 +327,24 @@ int main(int argc, char** argv) {
   if (q_offset && !min_q) { std::cerr << "--quality-offset goes with --min-base-quality <Q>." << std::endl; exit(1); }
   if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
   const bool split = !classified_out.empty() || !unclassified_out.empty();
+  // two names for one file: the same text, or the same inode when both exist
+  auto same_file = [](const std::string& a, const std::string& b) {
+    if (a.empty() || b.empty()) return false;
+    if (a == b) return true;
+    struct stat sa, sb;
+    return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+  };
+  if (!kmer_report.empty()) {      // refused before any device is touched
+    if (db_sharded) { std::cerr << "--kmer-report does not take --db-sharded: the sketches are counted behind one GPU's whole table." << std::endl; exit(1); }
+    for (int io : {i_objects, i_objects2})
+      if (io >= 0 && same_file(kmer_report, argv[io])) { std::cerr << "--kmer-report would overwrite the input: " << kmer_report << std::endl; exit(1); }
+    if (i_results >= 0 && same_file(kmer_report, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kmer-report would overwrite the result CSV: " << kmer_report << std::endl; exit(1); }
+    if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
+      std::cerr << "--kmer-report does not take list-of-files mode: classify the files one at a time." << std::endl;
+      exit(1);
+    }
+  }
   if (split) {      // refused before any device is touched
-    // two names for one file: the same text, or the same inode when both exist
-    auto same_file = [](const std::string& a, const std::string& b) {
-      if (a.empty() || b.empty()) return false;
-      if (a == b) return true;
-      struct stat sa, sb;
-      return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-    };
     if (i_objects2 > 0) { std::cerr << "--classified-out / --unclassified-out do not take paired-end input (-P): one -O file only." << std::endl; exit(1); }
     if (same_file(classified_out, unclassified_out)) { std::cerr << "--classified-out and --unclassified-out name the same file: " << classified_out << std::endl; exit(1); }
     for (const std::string* f : {&classified_out, &unclassified_out}) {
@@ -340,11 +356,11 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
-  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || split) && i_results < 0 && ext) {
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || split) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && !split)) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && !split)) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -364,6 +380,7 @@ int main(int argc, char** argv) {
   o.abund_filter = ab_filter;
   o.rank_report = rank_report; o.lineage = lineage;
   o.density = density;
+  o.kmer_report = kmer_report;
   o.classified_out = classified_out; o.unclassified_out = unclassified_out;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   o.low_complexity = (uint32_t)lowc;
@@ -397,6 +414,20 @@ int main(int argc, char** argv) {
       if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
         throw std::runtime_error("Failed to write the density report: " + density);
       std::cout << " - Density report stored in " << density << std::endl;
+    }
+    if (!kmer_report.empty()) {
+      std::vector<uint8_t> regs;
+      std::vector<uint64_t> hits;
+      classifier->ksketch_result(regs, hits);
+      const std::vector<uint64_t> ab = classifier->abundance_counts();
+      const std::vector<std::string>& names = classifier->target_names();
+      std::vector<const char*> nm(names.size());
+      for (size_t t = 0; t < names.size(); ++t) nm[t] = names[t].c_str();
+      const std::string report = mic::ksketch::format_report(nm.data(), ab.data() + 2, regs.data(), hits.data(), (uint32_t)names.size());
+      FILE* f = fopen(kmer_report.c_str(), "wb");
+      if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the k-mer report: " + kmer_report);
+      std::cout << " - K-mer report stored in " << kmer_report << std::endl;
     }
   } catch (const std::exception& ex) {
     std::cerr << ex.what() << std::endl;

@@ -68,6 +68,20 @@ inline uint32_t floor_hundredths(const std::string& s, uint32_t max_bin) {
   return m > max_bin ? max_bin : (uint32_t)m;
 }
 
+// num / den with `decimals` digits behind the point, rounded half up, from integer arithmetic (den != 0, decimals <= 9): "44.44", "1.00"
+inline std::string ratio_text(uint64_t num, uint64_t den, int decimals) {
+  unsigned __int128 scale = 1;
+  for (int j = 0; j < decimals; ++j) scale *= 10;
+  const unsigned __int128 q = ((unsigned __int128)num * scale + den / 2) / den;
+  const uint64_t whole = (uint64_t)(q / scale), frac = (uint64_t)(q % scale);
+  std::string out = std::to_string((unsigned long long)whole);
+  if (decimals > 0) {
+    const std::string f = std::to_string((unsigned long long)frac);
+    out += "." + std::string((size_t)decimals - f.size(), '0') + f;
+  }
+  return out;
+}
+
 }  // namespace decimal
 }  // namespace mic
 #endif

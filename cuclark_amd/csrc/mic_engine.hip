@@ -175,6 +175,7 @@ struct mic_engine {
   MicRollup rollup;                 // mic_rollup_*: the engine's lineage and counters (mic_rollup.hip)
   MicDensity density;               // mic_density_*: the engine's counters (mic_density.hip)
   MicSplit split;                   // mic_split_start / _stop: the engine's read-splitting setting (mic_split.hip)
+  MicKsketch ksketch;               // mic_ksketch_*: the engine's k-mer sketches (mic_ksketch.hip)
 };
 
 namespace {
@@ -617,6 +618,7 @@ uint32_t* mic_engine_low_complexity(mic_engine* e) { return &e->low_complexity; 
 MicRollup* mic_engine_rollup(mic_engine* e) { return &e->rollup; }
 MicDensity* mic_engine_density(mic_engine* e) { return &e->density; }
 MicSplit* mic_engine_split(mic_engine* e) { return &e->split; }
+MicKsketch* mic_engine_ksketch(mic_engine* e) { return &e->ksketch; }
 uint32_t mic_engine_row_words(const mic_engine* e) { return e->cfg.row_words; }
 hipStream_t mic_engine_stream(mic_engine* e) { return e->stream; }
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down) { *up = e->up_stream; *down = e->down_stream; }
@@ -721,6 +723,7 @@ int mic_destroy(mic_engine* e) {
   if (e->abund.d_counts) hipFree(e->abund.d_counts);
   if (e->rollup.d_counts) hipFree(e->rollup.d_counts);
   if (e->density.d_counts) hipFree(e->density.d_counts);
+  if (e->ksketch.d_regs) hipFree(e->ksketch.d_regs);
   if (e->rollup.d_block) hipFree(e->rollup.d_block);
   if (e->ev0) mic_event_put(e->ev0);
   if (e->ev1) mic_event_put(e->ev1);
@@ -1049,6 +1052,23 @@ int mic_batch_wait(mic_engine* e, size_t batch) {
       B.resolved = true;
     }
   }
+  return MIC_OK;
+}
+
+// the batch's reads into the engine's k-mer sketches (mic_ksketch_start): the same kernel the ingest path runs behind its query
+int mic_batch_ksketch(mic_engine* e, size_t batch) {
+  if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  Batch& B = e->batches[batch];
+  if (!B.scheduled) return fail(MIC_E_STATE, "batch %zu was not queried", batch);
+  const MicKsketch& ks = e->ksketch;
+  if (!ks.on || !ks.d_regs) return fail(MIC_E_STATE, "k-mer sketches were not started on this engine");
+  int rc = set_device(e);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(e->submit_mu);
+  HIPTRY(hipEventSynchronize(B.done));
+  HIPTRY(mic_launch_ksketch(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, B.n_reads, B.d_results, ks.n_targets, ks.d_regs, ks.d_hits,
+                            nullptr, B.stream));
+  HIPTRY(hipStreamSynchronize(B.stream));
   return MIC_OK;
 }
 

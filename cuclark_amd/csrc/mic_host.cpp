@@ -500,6 +500,41 @@ long mic_density_format(const uint64_t* counts, size_t n, int which, char* buf, 
 }
 }  // extern "C"
 
+// ---- k-mer sketches: the rule of mic_ksketch.h on the CPU, the estimator and the report as text ----------------------------------------
+#include "kmer_report.hpp"
+
+extern "C" {
+int mic_ksketch_add_host(const uint64_t* kmers, const uint32_t* labels, size_t n, int k, uint32_t n_targets, uint8_t* regs, uint64_t* hits) {
+  if (k < 1 || k > 32 || !regs || !hits || (n && (!kmers || !labels))) return MIC_E_INVALID;
+  const uint64_t cutoff = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t l = labels[i];
+    if (l == 0 || l > n_targets) continue;
+    if (kmers[i] & ~cutoff) return MIC_E_INVALID;            // (not a k-mer value; what came before it stays added)
+    const uint64_t h = mic_ksketch_hash(mic_ksketch_canonical(kmers[i], k));
+    uint8_t& reg = regs[((size_t)(l - 1) << MIC_KSKETCH_P) + mic_ksketch_index(h)];
+    const uint32_t rank = mic_ksketch_rank(h);
+    if (reg < rank) reg = (uint8_t)rank;
+    ++hits[l - 1];
+  }
+  return MIC_OK;
+}
+
+double mic_ksketch_estimate(const uint8_t* regs_of_one_target) {
+  if (!regs_of_one_target) return (double)MIC_E_INVALID;
+  return mic::ksketch::estimate(regs_of_one_target);
+}
+
+long mic_ksketch_format(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, uint32_t n_targets,
+                        char* buf, size_t cap) {
+  if (!names || !reads || !regs || !hits) return MIC_E_INVALID;
+  for (uint32_t t = 0; t < n_targets; ++t) if (!names[t]) return MIC_E_INVALID;
+  const std::string text = mic::ksketch::format_report(names, reads, regs, hits, n_targets);
+  if (buf && text.size() < cap) memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
+}
+}  // extern "C"
+
 // ---- base-quality mask: the rule of mic_qmask.h on the CPU (batches the host path classifies, the host merge of paired files) ------
 #include "mic_qmask.h"
 

@@ -40,6 +40,7 @@ void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
 MicAbund* mic_engine_abund(mic_engine* e);
 MicRollup* mic_engine_rollup(mic_engine* e);
 MicDensity* mic_engine_density(mic_engine* e);
+MicKsketch* mic_engine_ksketch(mic_engine* e);
 MicSplit* mic_engine_split(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
 uint32_t* mic_engine_low_complexity(mic_engine* e);
@@ -1189,6 +1190,9 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   if (!group || n_group == 0 || owner >= n_group) return mic_set_error(MIC_E_INVALID, "bad group");
   for (size_t p = 0; p < n_group; ++p) if (!group[p]) return mic_set_error(MIC_E_INVALID, "null engine in the group");
   mic_engine* e = group[owner];
+  // k-mer sketches count the k-mers of ONE engine's table behind ITS query: the table-sharded mode is not integrated
+  if (n_group > 1) for (size_t p = 0; p < n_group; ++p) if (mic_engine_ksketch(group[p])->on)
+    return mic_set_error(MIC_E_UNSUPPORTED, "k-mer sketches are started on an engine of a table-sharded group: not supported");
   const int paired = flags & MIC_INGEST_PAIRED;
   const bool no_csv = (flags & MIC_INGEST_NO_CSV) != 0;
   const uint32_t lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;      // lines per FASTQ record
@@ -1323,6 +1327,11 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     MicDensity& dn = *mic_engine_density(e);
     if (dn.on && dn.d_counts)
       ITRY(mic_launch_density(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ncu, dn.d_counts, s.d_hdr + H_STATUS, st));
+  }
+  {  // k-mer sketches (mic_ksketch_start on the slot's engine): a second probe pass over the reads that hit, under the same status word
+    MicKsketch& ks = *mic_engine_ksketch(e);
+    if (ks.on && ks.d_regs && ks.n_targets == nt)
+      ITRY(mic_launch_ksketch(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, ks.d_regs, ks.d_hits, s.d_hdr + H_STATUS, st));
   }
   if (no_csv && g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, st));
   ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));

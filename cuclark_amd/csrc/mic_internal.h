@@ -240,6 +240,21 @@ struct MicDensity {
 hipError_t mic_launch_density(const uint32_t* results, const uint32_t* norm, uint32_t norm_sub, size_t n, int k, uint32_t n_targets,
                               int n_cu, unsigned long long* counts, const uint32_t* status, hipStream_t s);
 
+// ---- k-mer sketches (mic_ksketch.hip; the kernel: mic_kernels.hip; the rule: mic_ksketch.h) ----------------------------------------
+// An engine's sketches while mic_ksketch_start is in force: one allocation on the engine's device, n_targets * MIC_KSKETCH_REGS
+// register bytes followed by n_targets u64 hit counters.
+struct MicKsketch {
+  uint8_t* d_regs = nullptr;
+  unsigned long long* d_hits = nullptr;
+  uint32_t n_targets = 0;
+  bool on = false;
+};
+// adds the k-mers of reads [0, n_reads) whose table label is a target to regs (max) and hits (sum) by the rule of mic_ksketch.h; a
+// read whose result row has sum 0 is skipped; regs 4-byte aligned; status as for mic_launch_abund; n_cu caps the grid
+hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const uint32_t* reads_ptr, const uint16_t* cont, size_t n_reads,
+                              const uint32_t* results, uint32_t n_targets, uint8_t* regs, unsigned long long* hits, const uint32_t* status,
+                              hipStream_t s);
+
 // ---- read splitting (mic_split.hip; the rule: mic_split.h) --------------------------------------------------------------------------
 // An engine's setting while mic_split_start is in force: every ingest batch it owns that returns MIC_INGEST_OK is partitioned.
 struct MicSplit {

@@ -13,6 +13,7 @@
 //     listed for the dense fallback kernels below, which are exact for any read.
 #include "mic_internal.h"
 #include "mic_device.h"
+#include "mic_ksketch.h"
 
 #include <stdlib.h>
 
@@ -2019,7 +2020,97 @@ __global__ void __launch_bounds__(256) probe_stats_kernel(const MicTable t, cons
   if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], nk); atomicAdd(&out[1], np); atomicAdd(&out[2], nh); atomicAdd(&out[3], nb); }
 }
 
+// ---- k-mer sketches (mic_ksketch.h: the rule): distinct k-mers hit per target -----------------------------------------------------
+// A second, scalar probe pass over the reads that hit, behind the query: one wavefront per read (the waves of a capped grid stride
+// over the batch), the wave leaves a read whose result row has sum 0 after one load.  Lanes stride the k-mer positions of each part
+// with dense_count_kernel's window extraction (any read length, any number of parts); a k-mer whose probe gives label l and that
+// this engine answers for (probe_any's `mine`) raises register idx of target l - 1 to its rank and counts one hit.
+//   register   a byte: the lane reads the aligned 32-bit word that holds it and skips when the byte is already >= rank; otherwise a
+//              compare-and-swap loop at device scope on that word.  The plain pre-read may be stale across XCDs.  That is harmless:
+//              registers only grow, so a stale value can only cause an unnecessary atomic, never a lost update.  (The loop continues
+//              from the value the failed swap returned, which is never stale.)
+//   hits       aggregated per wave the way tally_counts does: per distinct label among the hitting lanes one ballot, one popcount,
+//              one 64-bit atomic add from one lane.  Most reads have one or two labels.
+// No LDS.  All updates commute (max, add): the result does not depend on the order of lanes, waves, batches or engines.
+__device__ __forceinline__ void ksketch_raise(uint8_t* __restrict__ regs, size_t at, uint32_t rank) {
+  uint32_t* word = (uint32_t*)(regs + (at & ~(size_t)3));
+  const uint32_t sh = 8u * (uint32_t)(at & 3);
+  uint32_t old = *word;
+  while (((old >> sh) & 0xFFu) < rank) {
+    const uint32_t want = (old & ~(0xFFu << sh)) | (rank << sh);
+    if (__hip_atomic_compare_exchange_strong(word, &old, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+  }
+}
+
+template <bool KEY64>
+__global__ void __launch_bounds__(256) ksketch_kernel(const MicTable t, const uint32_t* __restrict__ reads_ptr,
+                                                      const uint16_t* __restrict__ cont, uint32_t n_reads,
+                                                      const uint32_t* __restrict__ results, uint32_t n_targets,
+                                                      uint8_t* __restrict__ regs, unsigned long long* __restrict__ hits,
+                                                      const uint32_t* __restrict__ status) {
+  if (status && *status) return;                  // the batch goes back to the host path, which adds it there
+  const int lane = threadIdx.x & 63;
+  const int k = t.k;
+  const uint64_t n_waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t r = (uint64_t)blockIdx.x * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); r < n_reads; r += n_waves) {
+    if (results[r * MIC_RESULT_WORDS] == 0) continue;          // no hit, no work (uniform in the wave)
+    uint32_t pp = reads_ptr[r];
+    const uint32_t pe = reads_ptr[r + 1];
+    while (pp < pe) {
+      const uint32_t plen = cont[pp];
+      if (plen == 0) break;
+      const uint32_t first = pp + 1;
+      pp = first + (plen + 7) / 8;
+      if (plen < (uint32_t)k) continue;
+      const uint32_t nk = plen - k + 1;
+      for (uint32_t base = 0; base < nk; base += 64) {         // uniform trip count: the ballots below see the whole wave
+        const uint32_t pos = base + lane;
+        uint32_t lab = 0;
+        if (pos < nk) {
+          // nucleotides [pos, pos+k): containers pos/8 .. (pos+k-1)/8, at most 5
+          const uint32_t c0 = first + pos / 8;
+          uint64_t hi = 0; uint32_t lo = 0;  // 80-bit window hi(64) : lo(16)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hi = (hi << 16) | (c0 + i < pp ? cont[c0 + i] : 0);
+          lo = c0 + 4 < pp ? cont[c0 + 4] : 0;
+          const int s = 2 * (pos & 7);
+          const uint64_t x = s ? ((hi << s) | ((uint64_t)lo >> (16 - s))) : hi;
+          const uint64_t kmer = x >> (64 - 2 * k);
+          bool mine = true;
+          const uint32_t m = probe_any<KEY64>(t, kmer, pos, &mine);
+          if (m && mine && m - 1 < n_targets) {
+            lab = m;
+            const uint64_t h = mic_ksketch_hash(canonical(kmer, k));
+            ksketch_raise(regs, ((size_t)(m - 1) << MIC_KSKETCH_P) + mic_ksketch_index(h), mic_ksketch_rank(h));
+          }
+        }
+        uint64_t mm = wballot(lab != 0);
+        while (mm) {
+          const uint32_t l1 = __builtin_amdgcn_readlane(lab, __builtin_ctzll(mm));
+          const uint64_t same = wballot(lab == l1);
+          mm &= ~same;
+          if (lane == __builtin_ctzll(same)) atomicAdd(&hits[l1 - 1], (unsigned long long)__builtin_popcountll(same));
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const uint32_t* reads_ptr, const uint16_t* cont, size_t n_reads,
+                              const uint32_t* results, uint32_t n_targets, uint8_t* regs, unsigned long long* hits, const uint32_t* status,
+                              hipStream_t s) {
+  if (!n_reads || !n_targets) return hipSuccess;
+  // four reads per block; a grid of at most 64 blocks per CU, whose waves then stride over the batch (reads differ in cost: the
+  // block scheduler evens the waves out, as for the query kernels)
+  size_t blocks = (n_reads + 3) / 4;
+  const size_t cap = (size_t)(n_cu > 0 ? n_cu : 256) * 64;
+  if (blocks > cap) blocks = cap;
+  if (slot_class == 64) ksketch_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, (uint32_t)n_reads, results, n_targets, regs, hits, status);
+  else ksketch_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, (uint32_t)n_reads, results, n_targets, regs, hits, status);
+  return hipGetLastError();
+}
 
 hipError_t mic_launch_probe_stats(const MicTable& t, int slot_class, const uint32_t* reads_ptr, const uint16_t* cont,
                                   size_t n_reads, unsigned long long* d_out, hipStream_t s) {

@@ -392,6 +392,31 @@ class MiClarkDB:
         """The rule on caller-owned device memory: counts ADDED to d_counts (u64[5153]); d_norm 0: every read in gamma bin 0."""
         check(self.L.mic_density_device(self.h, d_results, d_norm or None, n_reads, d_counts, stream or None))
 
+    # -- k-mer sketches (mic_ksketch_*): regs u8[num_targets, 16384] HyperLogLog registers, hits u64[num_targets] (csrc/mic_ksketch.h)
+    def ksketch_start(self):
+        """Allocate (num_targets * 16 KiB + 8 B), zero and enable the engine's sketches: every ingest batch that returns MIC_INGEST_OK
+        adds the k-mers of its reads that hit a target."""
+        check(self.L.mic_ksketch_start(self.h))
+
+    def ksketch_fetch(self):
+        """(regs u8[num_targets, 16384], hits u64[num_targets]) of the engine (waits for the device)."""
+        regs = np.zeros((self.num_targets, _lib.MIC_KSKETCH_REGS), np.uint8)
+        hits = np.zeros(self.num_targets, np.uint64)
+        check(self.L.mic_ksketch_fetch(self.h, regs.ctypes.data, regs.size, hits.ctypes.data, hits.size))
+        return regs, hits
+
+    def ksketch_stop(self):
+        check(self.L.mic_ksketch_stop(self.h))
+
+    def ksketch_device(self, d_reads_pointer, d_containers, n_reads, d_results, d_regs, d_hits, stream=0):
+        """The rule on caller-owned device memory (packed reads and result rows as for query_device): registers MAXED into d_regs
+        (u8[num_targets * 16384]), hits ADDED to d_hits (u64[num_targets]); reads whose result row has sum 0 are skipped."""
+        check(self.L.mic_ksketch_device(self.h, d_reads_pointer, d_containers, n_reads, d_results, d_regs, d_hits, stream or None))
+
+    def batch_ksketch(self, batch):
+        """Add the reads of a batch of the batch API (after its wait) to the engine's sketches."""
+        check(self.L.mic_batch_ksketch(self.h, batch))
+
     # -- rank roll-up (mic_rollup_*): a lineage is u16[n_levels, num_targets], level 1 first (host.rollup_check: its two conditions)
     def rollup_set(self, group_of):
         """Install a lineage on the engine (None or an empty array clears it)."""

@@ -198,6 +198,52 @@ def density_report(counts, which=0):
     return buf.raw[:n].decode()
 
 
+def ksketch_add(kmers, labels, k, n_targets, regs=None, hits=None):
+    """mic_ksketch_add_host: the sketch rule of csrc/mic_ksketch.h on (k-mer as it reads, label) pairs; label 0 or above n_targets adds
+    nothing, label l adds to target l - 1.  regs (u8[n_targets, 16384]) / hits (u64[n_targets]): arrays to ADD to, else fresh ones.
+    Returns (regs, hits)."""
+    L = _lib.load()
+    km = np.ascontiguousarray(kmers, np.uint64).reshape(-1)
+    lb = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+    assert km.size == lb.size, "one label per k-mer"
+    if regs is None:
+        regs = np.zeros((int(n_targets), _lib.MIC_KSKETCH_REGS), np.uint8)
+    if hits is None:
+        hits = np.zeros(int(n_targets), np.uint64)
+    assert regs.dtype == np.uint8 and regs.size == int(n_targets) * _lib.MIC_KSKETCH_REGS and regs.flags.c_contiguous
+    assert hits.dtype == np.uint64 and hits.size == int(n_targets) and hits.flags.c_contiguous
+    rc = L.mic_ksketch_add_host(km.ctypes.data, lb.ctypes.data, km.size, int(k), int(n_targets), regs.ctypes.data, hits.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_ksketch_add_host: invalid argument ({rc})")
+    return regs, hits
+
+
+def ksketch_estimate(regs):
+    """mic_ksketch_estimate: the number of distinct k-mers behind one target's 16384 registers (float; all zero: 0.0)."""
+    L = _lib.load()
+    r = np.ascontiguousarray(regs, np.uint8).reshape(-1)
+    assert r.size == _lib.MIC_KSKETCH_REGS, "the registers of one target"
+    return float(L.mic_ksketch_estimate(r.ctypes.data))
+
+
+def ksketch_report(names, reads, regs, hits):
+    """mic_ksketch_format: the report of exe/cuCLARK --kmer-report (csrc/kmer_report.hpp) as str.  names: one per target; reads: u64 per
+    target (what --abundance counts for it); regs, hits: the sketches."""
+    L = _lib.load()
+    n = len(names)
+    rd = np.ascontiguousarray(reads, np.uint64).reshape(-1)
+    rg = np.ascontiguousarray(regs, np.uint8).reshape(-1)
+    ht = np.ascontiguousarray(hits, np.uint64).reshape(-1)
+    assert rd.size == n and ht.size == n and rg.size == n * _lib.MIC_KSKETCH_REGS
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else bytes(s) for s in names])
+    ln = L.mic_ksketch_format(arr, rd.ctypes.data, rg.ctypes.data, ht.ctypes.data, n, None, 0)
+    if ln < 0:
+        raise ValueError(f"mic_ksketch_format: invalid argument ({ln})")
+    buf = C.create_string_buffer(ln + 1)
+    assert L.mic_ksketch_format(arr, rd.ctypes.data, rg.ctypes.data, ht.ctypes.data, n, buf, ln + 1) == ln
+    return buf.raw[:ln].decode()
+
+
 def rollup_check(n_targets, group_of):
     """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
     1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""

@@ -573,6 +573,44 @@ int mic_density_device(mic_engine* e, const uint32_t* d_results, const uint32_t*
 int mic_density_host(const uint32_t* results, const uint32_t* norm, size_t n_reads, int k, uint32_t n_targets, uint64_t* counts);
 long mic_density_format(const uint64_t* counts, size_t n, int which, char* buf, size_t cap);
 
+/* ---- k-mer sketches: distinct k-mers hit per target, sketched on the device (csrc/mic_ksketch.h: the rule, shared by host and device) ----
+ * For every k-mer occurrence of every read whose table label is target t (what the query counts: per read part, none across an 'N',
+ * masked bases included) the canonical k-mer goes into t's HyperLogLog sketch and t's hit counter grows by one:
+ *   regs   u8[num_targets * MIC_KSKETCH_REGS]: register idx of target t (0-based) at regs[t * MIC_KSKETCH_REGS + idx]
+ *   hits   u64[num_targets]
+ * Registers merge by element-wise max and hits by sum: batches, engines and calls combine in any order with the same result.  The
+ * rule does not depend on a confidence or gamma filter.
+ * mic_ksketch_device    the rule on caller-owned device memory: packed reads as for mic_query_device, d_results the reads' result rows
+ *                       (MIC_RESULT_WORDS u32 per read: a read whose sum is 0 is skipped), registers MAXED into d_regs and hits ADDED
+ *                       into d_hits.  Only the k-mers this engine answers for count, so the sum over the engines of a sharded or parted
+ *                       table is the whole table's.  Asynchronous on `stream` (NULL = the engine's stream).
+ * mic_ksketch_start / _fetch / _stop   the engine's sketches (num_targets * 16 KiB + 8 B on its device, allocated and zeroed at
+ *                       start, freed with the engine) over ingest batches, by the contract of mic_abundance_start / _fetch / _stop:
+ *                       a mic_ingest_classify batch that returns MIC_INGEST_OK is added behind the query on the slot's stream, with
+ *                       or without MIC_INGEST_NO_CSV; a batch handed back adds nothing (the caller classifies it through the batch
+ *                       API and adds it with mic_batch_ksketch).  While started, mic_ingest_classify_group with more than one engine
+ *                       returns MIC_E_UNSUPPORTED.  _fetch: n_regs = num_targets * MIC_KSKETCH_REGS, n_hits = num_targets.
+ * mic_batch_ksketch     adds the reads of a batch of the batch API (after mic_batch_wait; its packed reads and results are still on
+ *                       the device) to the engine's sketches.  MIC_E_STATE when they are not started.  Synchronous.
+ * mic_ksketch_add_host  the rule on the CPU (no device needed) on n pairs (k-mer as it reads, label): label 0 or above n_targets
+ *                       adds nothing, label l adds to target l - 1.
+ * mic_ksketch_estimate  the number of distinct k-mers behind one target's MIC_KSKETCH_REGS registers (Ertl's improved raw estimator);
+ *                       all registers zero: 0.  A negative value when regs is NULL.
+ * mic_ksketch_format    the report of exe/cuCLARK --kmer-report (csrc/kmer_report.hpp) as text: names (n_targets strings), reads per
+ *                       target (n_targets u64: what mic_abundance_* counts for it), the sketches.  Returns the length of the text
+ *                       (written with a terminator when it fits cap; buf may be NULL to ask for the length) or MIC_E_INVALID. */
+#define MIC_KSKETCH_REGS 16384
+int mic_ksketch_device(mic_engine* e, const uint32_t* d_reads_pointer, const uint16_t* d_containers, size_t n_reads, const uint32_t* d_results,
+                       uint8_t* d_regs, uint64_t* d_hits, void* stream);
+int mic_ksketch_start(mic_engine* e);
+int mic_ksketch_fetch(mic_engine* e, uint8_t* regs, size_t n_regs, uint64_t* hits, size_t n_hits);
+int mic_ksketch_stop(mic_engine* e);
+int mic_batch_ksketch(mic_engine* e, size_t batch);
+int mic_ksketch_add_host(const uint64_t* kmers, const uint32_t* labels, size_t n, int k, uint32_t n_targets, uint8_t* regs, uint64_t* hits);
+double mic_ksketch_estimate(const uint8_t* regs_of_one_target);
+long mic_ksketch_format(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, uint32_t n_targets,
+                        char* buf, size_t cap);
+
 /* ---- read splitting: the classified and the unclassified reads themselves, partitioned on the device (csrc/mic_split.h: the rule) ----
  * The reference says what every read is and cannot hand the reads back.  Record r of a text is the bytes from the first byte of its
  * header line up to the first byte of the next record's header line (the last record: to the end of the text); records are those of

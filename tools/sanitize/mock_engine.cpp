@@ -206,6 +206,15 @@ int mic_abundance_stop(mic_engine*) { return MIC_OK; }
 int mic_density_start(mic_engine*) { return MIC_OK; }
 int mic_density_fetch(mic_engine*, uint64_t* counts, size_t n) { for (size_t i = 0; i < n; ++i) counts[i] = 0; return MIC_OK; }
 int mic_density_stop(mic_engine*) { return MIC_OK; }
+// k-mer sketches: likewise, the mock probes nothing a second time (mic_ksketch_add_host / _estimate / _format are mic_host.cpp's)
+int mic_ksketch_start(mic_engine*) { return MIC_OK; }
+int mic_ksketch_fetch(mic_engine*, uint8_t* regs, size_t n_regs, uint64_t* hits, size_t n_hits) {
+  memset(regs, 0, n_regs);
+  for (size_t i = 0; i < n_hits; ++i) hits[i] = 0;
+  return MIC_OK;
+}
+int mic_ksketch_stop(mic_engine*) { return MIC_OK; }
+int mic_batch_ksketch(mic_engine*, size_t) { return MIC_OK; }
 // roll-up counters: likewise (the host path's batches are counted by mic_rollup_host, which is mic_host.cpp's and under test)
 int mic_rollup_set(mic_engine*, uint32_t, const uint16_t*) { return MIC_OK; }
 int mic_rollup_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
