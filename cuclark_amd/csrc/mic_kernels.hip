@@ -14,8 +14,10 @@
 #include "mic_internal.h"
 #include "mic_device.h"
 #include "mic_ksketch.h"
+#include "mic_join2.h"      // query_kernel_r: a read of two parts as one joined window, and its host model
 
 #include <stdlib.h>
+#include <type_traits>
 
 #ifndef MIC_EXP
 #define MIC_EXP 0
@@ -493,10 +495,17 @@ __device__ __forceinline__ void sliding_min_rows(uint32_t& a0, uint32_t& a1, uin
 // ln: the lane number as an opaque per-chunk copy (what is derived from it - compare masks - is recomputed per chunk: kept across
 // the kernel they would live in scalar register pairs the per-run kernel does not have); lane_inv: the lane number the compiler
 // may hoist from (vector registers are plentiful: shift counts and permute addresses stay resident, 8 VALU per chunk fewer).
-template <bool CANON>
-__device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_inv, int k, int m, bool past, uint32_t& qa0, uint32_t& qa1) {
+// GAP (query_kernel_r, a read of two parts joined at nucleotide len1 - mic_join2.h): the t-mers of part 2 carry their position in
+// the part, so the position bits differ between the passes.
+template <bool CANON, bool GAP = false>
+__device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_inv, int k, int m, bool past, uint32_t& qa0, uint32_t& qa1,
+                                                  uint32_t len1 = 0) {
   const int w = k - m + 1, t = s_tlen(k, m), W = k - t + 1;
-  const uint32_t pb = (uint32_t)lane_inv & 31u;                     // chunks start at multiples of 128: position & 31 = lane & 31 in every pass
+  const uint32_t pb0 = (uint32_t)lane_inv & 31u;                    // chunks start at multiples of 128: position & 31 = lane & 31 in every pass
+  auto pb_of = [&](int h) {
+    const uint32_t pos = 64u * (uint32_t)h + (uint32_t)lane_inv;
+    return GAP ? (pos - j2_part_offset(pos, len1)) & 31u : pb0;
+  };
   uint32_t a0, a1, a2 = 0xFFFFFFFFu;
   if (t <= 16) {
     // the t-mer at position P = 64 h + lane: 16 nucleotides from P on are one funnel shift of window dwords (P - 1) / 16 and
@@ -508,7 +517,7 @@ __device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_
       const uint32_t W0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad + 16 * h, (int)wd), W1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad + 16 * h + 4, (int)wd);
       uint32_t tv = __builtin_amdgcn_alignbit(W0, W1, tsh) >> (32 - 2 * t);
       if (CANON) { const uint32_t tr = revcomp_bits32(tv, t); tv = tr < tv ? tr : tv; }
-      return ((t <= 12 ? s_torder24(tv) : s_torder(tv)) & ~31u) | pb;
+      return ((t <= 12 ? s_torder24(tv) : s_torder(tv)) & ~31u) | pb_of(h);
     };
     a0 = tkey(0); a1 = tkey(1);
     if (past) a2 = tkey(2);
@@ -518,7 +527,7 @@ __device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_
       const uint32_t d0 = bperm(idx, wd), d1 = bperm(idx + 1, wd), d2 = bperm(idx + 2, wd);
       uint64_t tv = kmer_from_dwords(d0, d1, d2, lane_inv & 15, t);
       if (CANON) { const uint64_t tr = revcomp_bits(tv, t); tv = tr < tv ? tr : tv; }
-      return (s_torder(tv) & ~31u) | pb;
+      return (s_torder(tv) & ~31u) | pb_of(h);
     };
     a0 = tkey(0); a1 = tkey(1);
     if (past) a2 = tkey(2);
@@ -526,7 +535,7 @@ __device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_
   if (W >= 16) sliding_min_rows(a0, a1, a2, W, ln, lane_inv);
   else sliding_min3(a0, a1, a2, W, ln);
   // position of the minimal t-mer inside the k-mer, then of the sampled m-mer: i mod w
-  uint32_t d0 = (a0 - pb) & 31u, d1 = (a1 - pb) & 31u;
+  uint32_t d0 = (a0 - pb_of(0)) & 31u, d1 = (a1 - pb_of(1)) & 31u;
   if (W == 2 * w) { const uint32_t e0 = d0 - (uint32_t)w, e1 = d1 - (uint32_t)w; d0 = e0 < d0 ? e0 : d0; d1 = e1 < d1 ? e1 : d1; }
   else if (W != w) {
     const uint32_t rcp = (1024u + (uint32_t)w - 1u) / (uint32_t)w;      // d < 32, w <= 16: (d * rcp) >> 10 = d / w exactly
@@ -548,14 +557,17 @@ __device__ __forceinline__ void sampled_positions(uint32_t wd, int ln, int lane_
 // resident next to the five fetch addresses: 8 bytes of scratch in the two-strand instantiations).
 // s0 .. s2: chunk position of the sampled m-mer of k-mers 3 lane + 0 .. 2 (below 256 whatever the lane holds); q0 .. q2: the same, or
 // ~0 - an inline constant - for the k-mers past n_act; p0: 3 lane.
-template <bool CANON>
+// GAP (a read of two parts joined at nucleotide len1 - mic_join2.h): the keys carry the position inside the part (one offset per lane:
+// j2_part_offset), and the k-mers at [g0, g0 + k - 1), which span the junction, leave as ~0 like those past n_act.
+template <bool CANON, bool GAP = false>
 __device__ __forceinline__ void sampled_positions3(uint32_t wd, int lane_inv, uint32_t n_act, uint32_t& p0, uint32_t& s0, uint32_t& s1, uint32_t& s2,
-                                                    uint32_t& q0, uint32_t& q1, uint32_t& q2) {
+                                                    uint32_t& q0, uint32_t& q1, uint32_t& q2, uint32_t len1 = 0, uint32_t g0 = 0) {
   const int at = lane_inv << 2;
   const int ad = f3_dword(lane_inv) << 2;
   const uint32_t tsh = f3_shift(lane_inv);
   p0 = 3u * (uint32_t)lane_inv;
-  const uint32_t np0 = 0u - p0;
+  const uint32_t pk = GAP ? p0 - j2_part_offset(p0 + 2u, len1) : p0;      // the position the keys carry
+  const uint32_t np0 = 0u - pk;
   const uint32_t W0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad, (int)wd), W1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ad + 4, (int)wd);
   const uint32_t X = __builtin_amdgcn_alignbit(W0, W1, tsh);
   uint32_t t0 = f3_tmer(X, 0), t1 = f3_tmer(X, 1), t2 = f3_tmer(X, 2);
@@ -567,7 +579,7 @@ __device__ __forceinline__ void sampled_positions3(uint32_t wd, int lane_inv, ui
   }
   // (h & ~31) | (pos & 31) = f3_key: bits of pos where the constant 31 has them, of h elsewhere (truth table 0xD8 over h, pos, 31)
   auto key = [](uint32_t tv, uint32_t pos) { return (uint32_t)__builtin_amdgcn_bitop3_b32(s_torder24(tv), pos, 31u, 0xD8); };
-  const uint32_t k0 = key(t0, p0), k1 = key(t1, p0 + 1u), k2 = key(t2, p0 + 2u);
+  const uint32_t k0 = key(t0, pk), k1 = key(t1, pk + 1u), k2 = key(t2, pk + 2u);
   const uint32_t T = f3_min3(k0, k1, k2), e12 = f3_min(k1, k2), e01 = f3_min(k0, k1);
   // (ds_bpermute wraps the lane number by itself)
   const uint32_t x1 = (uint32_t)__builtin_amdgcn_ds_bpermute(at + 4, (int)T);
@@ -583,9 +595,13 @@ __device__ __forceinline__ void sampled_positions3(uint32_t wd, int lane_inv, ui
     const uint32_t d = (r + np0 - j) & 31u, e = d - (uint32_t)F3_WM;
     return f3_min(d, e) + p0 + j;
   };
-  const int nv = (int)(n_act + np0);               // k-mers of the chunk from 3 lane on
+  const int nv = GAP ? (int)(n_act - p0) : (int)(n_act + np0);               // k-mers of the chunk from 3 lane on
   s0 = sampled(r0, 0u); s1 = sampled(r1, 1u); s2 = sampled(r2, 2u);
   q0 = nv > 0 ? s0 : ~0u; q1 = nv > 1 ? s1 : ~0u; q2 = nv > 2 ? s2 : ~0u;
+  if (GAP) {
+    const uint32_t gv = p0 - g0;                   // j2_is_kmer: position - g0 >= k - 1, or the k-mer spans the junction
+    q0 = gv >= (uint32_t)(F3_K - 1) ? q0 : ~0u; q1 = gv + 1u >= (uint32_t)(F3_K - 1) ? q1 : ~0u; q2 = gv + 2u >= (uint32_t)(F3_K - 1) ? q2 : ~0u;
+  }
 }
 
 #ifndef MIC_SPEC
@@ -1311,8 +1327,9 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
   // HALF of its next read (window, sampled positions, runs, regions, slot hashes: ~60 % of a read's vector work, no memory access
   // of its own); only then it waits, compares and tallies the earlier read.  What lives across: the run lanes' region words,
   // range of positions, slot (7 VGPRs) and three scalars.  ONE stage area still: the next read's slot list is written after
-  // the earlier read's slots have been consumed.  Reads that are not one round of one chunk of one part (long reads, several
-  // parts, more than 32 runs) drain the pipeline and take the plain road: front / setup / issue / consume one after the other.
+  // the earlier read's slots have been consumed.  Reads that are not one round of one chunk of one part - or of two parts joined,
+  // round 9, below - (long reads, three or more parts, more than 32 runs) drain the pipeline and take the plain road: front /
+  // setup / issue / consume one after the other.
   // Measured (headline, 10 M x 150 bp, 119 GB table): 4.63 -> 4.37-4.45 ms by HIP events, 241 VALU + 172 SALU + 45 branches per read
   // against 240 + 167 + 40: the vector unit 89 % busy instead of 85 %.  One-strand table: 4.97 -> 4.83 ms.
   //
@@ -1328,12 +1345,34 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     uint32_t G0, G1, G2, cur;
     int jmax, jmin, remaining;
   };
+  // A READ OF TWO PARTS on the pipelined road (round 9; mic_join2.h has the arithmetic and the host model).  An N inside a 150-bp
+  // read leaves two parts; where both hold k-mers the read used to drain the pipeline and run front / setup / issue / consume once
+  // per part, the second part's window by global loads: ~480 VALU instead of ~250, for 8 % of the reads of a FASTQ with 0.1 % N.
+  // Such a read - both parts and what ends it inside the read-ahead entry, at most 128 k-mer positions together - now runs ONCE: the
+  // window is part 1 followed at once by part 2 (out of the entry in LDS), the k - 1 k-mer positions that span the junction carry
+  // the sentinel of the positions past the read (no run continues across them; the stretch itself is one record whose lane the
+  // set-up disables), and everything in front of and behind them has the windows, keys, runs and records it has per part.  The
+  // joined front half is an instantiation of its own of `front` (gp: Gap instead of NoGap); the set-up of the pipelined road is
+  // shared and compares the record's k-mer with the junction's first position (see `step`): a one-part read pays that compare.
+  struct NoGap {};
+  struct Gap { uint32_t len1, b2, g0; };          // J2Shape's: nucleotides of part 1, u16 of part 2's first container in the entry, first junction position (~0: none)
   // front half of a chunk: window word, sampled positions, run records in LDS; returns the number of runs
-  auto front = [&](const uint32_t first, const uint32_t cend, const uint32_t base, const uint32_t nk, const bool use_ahead, uint32_t& wd_out) __attribute__((always_inline)) -> uint32_t {
+  auto front = [&](const uint32_t first, const uint32_t cend, const uint32_t base, const uint32_t nk, const bool use_ahead, uint32_t& wd_out,
+                   const auto gp) __attribute__((always_inline)) -> uint32_t {
+    constexpr bool GAP = std::is_same<decltype(gp), const Gap>::value;
     int ln = lane;
     asm volatile("" : "+v"(ln));
-    const uint32_t wd = use_ahead ? ahead_word(ahead_sel ? ahead0 : ahead1, cur_pp)
-                                  : window_word_w(cont, first, cend, base, ln, false, 0u);
+    uint32_t wd;
+    if constexpr (GAP) {
+      // (the entry is 64 dwords: a lane past the window reads inside it whatever it computes - j2_dword(j < 12) + 1 <= 22)
+      const uint32_t* entry = ahead_sel ? ahead0 : ahead1;
+      const uint32_t j = (uint32_t)ln < 12u ? (uint32_t)ln : 0u;
+      const uint32_t d = j2_dword(j, gp.len1, gp.b2);
+      wd = j2_window(ahead_word(entry, cur_pp), entry[d], entry[d + 1u], j, gp.len1, gp.b2);
+    } else {
+      wd = use_ahead ? ahead_word(ahead_sel ? ahead0 : ahead1, cur_pp)
+                     : window_word_w(cont, first, cend, base, ln, false, 0u);
+    }
     wd_out = wd;
     const uint32_t n_act = nk - base < 128u ? nk - base : 128u;
     if constexpr (KK == F3_K && MM == F3_M) {
@@ -1341,7 +1380,8 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
       // exists, 3 x 64 > 128 - counts as ~0 and leads the closing record (only the k-mer of a closing record is ever read: its low
       // byte is whatever the lane computed)
       uint32_t p0, s0, s1, s2, q0, q1, q2;
-      sampled_positions3<!FWD>(wd, lane, n_act, p0, s0, s1, s2, q0, q1, q2);
+      if constexpr (GAP) sampled_positions3<!FWD, true>(wd, lane, n_act, p0, s0, s1, s2, q0, q1, q2, gp.len1, gp.g0);
+      else sampled_positions3<!FWD>(wd, lane, n_act, p0, s0, s1, s2, q0, q1, q2);
       const uint32_t pv = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)q2, 0x138, 0xF, 0xF, false);
       const bool f0 = q0 != pv, f1 = q1 != q0, f2 = q2 != q1;
       const uint64_t b0 = wballot(f0), b1 = wballot(f1), b2 = wballot(f2);
@@ -1360,9 +1400,14 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     }
     const bool past = n_act + (uint32_t)(k - s_tlen(k, m)) >= 129u;
     uint32_t qa0, qa1;
-    sampled_positions<!FWD>(wd, ln, lane, k, m, past, qa0, qa1);
+    if constexpr (GAP) sampled_positions<!FWD, true>(wd, ln, lane, k, m, past, qa0, qa1, gp.len1);
+    else sampled_positions<!FWD>(wd, ln, lane, k, m, past, qa0, qa1);
     qa0 = (uint32_t)lane < n_act ? qa0 : 0xFFu;
     qa1 = 64u + (uint32_t)lane < n_act ? qa1 : 0xFFu;
+    if constexpr (GAP) {                               // j2_is_kmer: the k-mers that span the junction
+      qa0 = (uint32_t)lane - gp.g0 >= (uint32_t)(k - 1) ? qa0 : 0xFFu;
+      qa1 = 64u + (uint32_t)lane - gp.g0 >= (uint32_t)(k - 1) ? qa1 : 0xFFu;
+    }
     const uint32_t last0 = __builtin_amdgcn_readlane(qa0, 63);
     uint32_t p0 = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)qa0, 0x138, 0xF, 0xF, false);
     uint32_t p1 = (uint32_t)__builtin_amdgcn_update_dpp((int)last0, (int)qa1, 0x138, 0xF, 0xF, false);
@@ -1390,13 +1435,15 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
       lo = (uint32_t)x; hi = (uint32_t)(x >> 32);
     }
   };
-  auto setup = [&](const uint32_t wd, const uint32_t rbase, const uint32_t R, Round& L, uint32_t& nrun_out) __attribute__((always_inline)) {
+  auto setup = [&](const uint32_t wd, const uint32_t rbase, const uint32_t R, Round& L, uint32_t& nrun_out, const auto gp) __attribute__((always_inline)) {
+    constexpr bool GAP = std::is_same<decltype(gp), const Gap>::value;
     const uint32_t nrun = R - rbase < MIC_RMAX ? R - rbase : MIC_RMAX;
     nrun_out = nrun;
-    const bool vr = (uint32_t)lane < nrun;
+    bool vr = (uint32_t)lane < nrun;
     const uint32_t ri = vr ? rbase + (uint32_t)lane : 0u;
     const uint32_t rc0 = rec[ri], rc1 = rec[ri + 1];
     const int qa = (int)(rc0 & 255u), i0 = (int)(rc0 >> 8);
+    if constexpr (GAP) vr = vr && (uint32_t)i0 != gp.g0;      // the record of the junction's positions: no run (whatever its low byte holds)
     const int n = (int)(rc1 >> 8) - i0;
     const int s1 = qa - ctx - 1;
     const int D = s1 >> 4;
@@ -1616,6 +1663,7 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     // per CU) is what the kernel is short of, and the loops' bookkeeping is scalar work a 150-bp read does not need.
     bool shape = false, simple = false;
     uint32_t n_nrun = 0, plen0 = 0, pp1 = 0;
+    uint32_t slot2 = J2_NONE;                                 // the slot behind the first part, where the entry holds it (j2_slot2)
     if (have) {
       plen0 = cur_hdr; pp1 = pp + 1 + (plen0 + 7) / 8;
       shape = plen0 - (uint32_t)k < 128u && pp1 == pe;       // (k <= plen0 < k + 128 by the unsigned wrap; pp1 == pe implies pp < pe)
@@ -1623,14 +1671,29 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
         const uint32_t rel = pp1 - cur_pp + (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);
         if (rel < 24u) {
           const uint32_t v = (ahead_sel ? ahead0 : ahead1)[rel >> 1];
-          shape = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu) == 0;
+          slot2 = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu);
+          shape = slot2 == 0;
         }
       }
+      // ONE set-up behind either front half: with a set-up of its own for the joined read the run lanes' state would be merged from
+      // three sides (two set-ups and, for a read of the plain road, what it held before), and the one-part road paid 14 v_mov per
+      // read for that merge.  So the set-up takes the junction's first position as a scalar - no position for a one-part read - and
+      // the one-part road pays one compare.
+      uint32_t n_wd = 0, R = MIC_RMAX + 1u, g0 = 0xFFFFFFFFu;
       if (PIPE && shape) {                                    // ... and at most one round of runs: the pipelined road
-        uint32_t n_wd;
-        const uint32_t R = front(pp + 1, pp1, 0u, plen0 - (uint32_t)k + 1u, true, n_wd);
-        if (R <= MIC_RMAX) { setup(n_wd, 0u, R, N, n_nrun); simple = true; }
+        R = front(pp + 1, pp1, 0u, plen0 - (uint32_t)k + 1u, true, n_wd, NoGap{});
+      } else if constexpr (PIPE) {
+        // two parts that fit one chunk, everything inside the read-ahead entry (j2_shape; scalar work): the same road, joined
+        const uint32_t odd = (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);
+        const uint32_t* entry = ahead_sel ? ahead0 : ahead1;
+        const J2Shape j2 = j2_shape(plen0, slot2, pe - pp, odd, (uint32_t)k,
+                                    [&](uint32_t u) { return (uint32_t)__builtin_amdgcn_readfirstlane(j2_half(entry[u >> 1], u)); });
+        if (__builtin_expect(j2.ok != 0u, 0)) {
+          R = front(pp + 1, pp1, 0u, j2.n_act, true, n_wd, Gap{j2.len1, j2.b2, j2.g0});
+          g0 = j2.g0;
+        }
       }
+      if (PIPE && R <= MIC_RMAX) { setup(n_wd, 0u, R, N, n_nrun, Gap{0u, 0u, g0}); simple = true; }
     }
     // the earlier read: its slots have had the front half above to arrive
     if (PIPE && p_valid) {
@@ -1647,10 +1710,10 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
       uint32_t n_ent = 0, overflow = 0, total = 0, cg = MIC_CG_NONE;
       auto chunk = [&](const uint32_t first, const uint32_t cend, const uint32_t base, const uint32_t nk, const bool use_ahead) __attribute__((always_inline)) {
         uint32_t wd;
-        const uint32_t R = front(first, cend, base, nk, use_ahead, wd);
+        const uint32_t R = front(first, cend, base, nk, use_ahead, wd, NoGap{});
         for (uint32_t rbase = 0; rbase < R; rbase += MIC_RMAX) {
           Round L; uint32_t nrun;
-          setup(wd, rbase, R, L, nrun);
+          setup(wd, rbase, R, L, nrun, NoGap{});
           issue(L.cur, nrun);
           consume(L, acc, n_ent, overflow, total, cg);
         }
