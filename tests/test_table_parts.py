@@ -33,7 +33,12 @@ def _engine(k, T, **kw):
 
 def _genome_db(rng, G, k, htsize, T, stride=40000):
     """Every k-mer of a random genome, labelled by position: the database the super-k-mer layouts are made for (long runs)."""
-    codes = rng.integers(0, 4, G, dtype=np.uint8)
+    return _db_of_codes(rng.integers(0, 4, G, dtype=np.uint8), k, htsize, T, stride)
+
+
+def _db_of_codes(codes, k, htsize, T, stride=40000):
+    """the same of a genome given as nucleotide codes (T=0 G=1 C=2 A=3)"""
+    G = codes.size
     v = np.zeros(G - k + 1, np.uint64)
     for j in range(k):
         v = (v << np.uint64(2)) | codes[j:j + G - k + 1].astype(np.uint64)
@@ -91,6 +96,7 @@ def _merge_rows(k, T, row_words, rows_list, n):
             e.sync()
             acc = out
         results = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()       # the engine's stream does not wait for torch's: the zeros must be there before its kernel writes
         e.result_from_rows_device(acc.data_ptr(), results.data_ptr(), n)
         e.sync()
         return acc.cpu().numpy().view(np.uint32), results.cpu().numpy().view(np.uint32)

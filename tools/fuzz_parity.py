@@ -111,7 +111,7 @@ def make_case(seed, pack):
     import golden_util as gu
     o = gu.oracle()
     rng = np.random.default_rng(seed)
-    k = int(rng.choice([8, 12, 16, 20, 21, 24, 25, 27, 31, 32]))
+    k = int(rng.choice([8, 12, 16, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32]))
     htsize = int(rng.choice([2, 97, 1009, 4096, 65537, 99991, 1 << 20, 999983, 57777779]))
     key_bytes = o.key_bytes_rule(htsize, k)
     n_elems = int(rng.integers(50, 120000))
