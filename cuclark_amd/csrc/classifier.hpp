@@ -40,6 +40,7 @@ struct Options {
   std::string kmer_report;                                   // --kmer-report <file>: distinct k-mers hit per target are sketched (mic_ksketch_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
   std::string classified_out, unclassified_out;              // --classified-out / --unclassified-out <file>: the reads themselves, split (mic_split_*)
+  std::string hit_maps;                                      // --hit-maps <file>: per read the runs of k-mer assignments along it (mic_hitmap_*)
   uint32_t low_complexity = 0;                               // --mask-low-complexity <level>: DUST level in [1,149], 0 = off (mic_lowc.h)
 };
 
@@ -144,6 +145,12 @@ class Classifier {
   int splitting() const { return (opt_.classified_out.empty() ? 0 : MIC_SPLIT_CLASSIFIED) | (opt_.unclassified_out.empty() ? 0 : MIC_SPLIT_UNCLASSIFIED); }
   int split_fd_[2] = {-1, -1};                // run_segments: the two files, written in order
   std::string* split_sink_[2] = {nullptr, nullptr};
+  // --hit-maps: the streaming path takes every batch's text from its engine (mic_ingest_hitmap_text); what stays on the host goes
+  // through mic_batch_hitmap + mic_hitmap_format in process_segment, into the run's file or - a batch the streaming path handed back -
+  // into the sink
+  bool mapping() const { return !opt_.hit_maps.empty(); }
+  int hitmap_fd_ = -1;                        // run_segments: the file, written in order
+  std::string* hitmap_sink_ = nullptr;
   rank::Lineage lineage_;
   std::vector<uint64_t> host_rollup_;
   void reset_counts();

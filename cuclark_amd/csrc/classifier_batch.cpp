@@ -48,6 +48,20 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
     split_fd_[c] = open(split_name[c]->c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
     if (split_fd_[c] == -1) { std::cerr << "Failed to create/open file: " << *split_name[c] << std::endl; if (fout) fclose(fout); if (c && split_fd_[0] != -1) { close(split_fd_[0]); split_fd_[0] = -1; } return; }
   }
+  // --hit-maps: the file with its header line; process_segment appends every segment's text in order
+  hitmap_fd_ = -1;
+  if (mapping()) {
+    unlink(opt_.hit_maps.c_str());
+    hitmap_fd_ = open(opt_.hit_maps.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    const size_t hl = strlen(MIC_HITMAP_HEADER);
+    if (hitmap_fd_ == -1 || write(hitmap_fd_, MIC_HITMAP_HEADER, hl) != (ssize_t)hl) {
+      std::cerr << "Failed to create/open file: " << opt_.hit_maps << std::endl;
+      if (hitmap_fd_ != -1) { close(hitmap_fd_); hitmap_fd_ = -1; }
+      if (fout) fclose(fout);
+      for (int c = 0; c < 2; ++c) if (split_fd_[c] != -1) { close(split_fd_[c]); split_fd_[c] = -1; }
+      return;
+    }
+  }
   reset_counts();
   struct timeval t0, t1;
   gettimeofday(&t0, nullptr);
@@ -84,6 +98,7 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
   if (fout && (fclose(fout) != 0 || write_failed)) { if (err.empty()) err = "cannot write " + csv + " (disk full?)"; }
   for (int c = 0; c < 2; ++c)
     if (split_fd_[c] != -1) { if (close(split_fd_[c]) != 0 && err.empty()) err = "cannot write " + *split_name[c] + " (disk full?)"; split_fd_[c] = -1; }
+  if (hitmap_fd_ != -1) { if (close(hitmap_fd_) != 0 && err.empty()) err = "cannot write " + opt_.hit_maps + " (disk full?)"; hitmap_fd_ = -1; }
   release_batches();
   if (!err.empty()) die(err);
   gettimeofday(&t1, nullptr);
@@ -167,6 +182,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
 
   // ---- batches: pack -> query -> wait -> format; ordered write
   std::vector<std::string> out(nb_total);
+  std::vector<std::string> hm_out(mapping() ? nb_total : 0);       // --hit-maps: every batch's text, written in the same order
   std::vector<char> ready(nb_total, 0);
   std::mutex wmu;
   size_t next_write = 0;
@@ -203,6 +219,22 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
         check(mic_batch_query(engines_[d], lb, (opt_.extended || ranking()) ? 1 : 0, 0), "queryBatch");
         check(mic_batch_wait(engines_[d], lb), "waitForBatch");
         if (sketching()) check(mic_batch_ksketch(engines_[d], lb), "k-mer sketches");      // (the batch's packed reads and results are still on the device)
+        if (mapping()) {     // likewise: the maps of the batch's reads (sized, then fetched), as text with the names this path has
+          uint64_t nw = 0;
+          std::vector<uint32_t> hm_off(cnt + 1, 0), hm_words;
+          check(mic_batch_hitmap(engines_[d], lb, hm_off.data(), hm_off.size(), nullptr, 0, &nw), "hit maps");
+          hm_words.resize((size_t)nw);
+          if (nw) check(mic_batch_hitmap(engines_[d], lb, hm_off.data(), hm_off.size(), hm_words.data(), hm_words.size(), &nw), "hit maps");
+          std::vector<std::string> rn(cnt);
+          std::vector<const char*> rnp(cnt);
+          for (size_t i = 0; i < cnt; ++i) { rn[i].assign((const char*)map + name_s[r0 + i], (size_t)(name_e[r0 + i] - name_s[r0 + i])); rnp[i] = rn[i].c_str(); }
+          const long len = mic_hitmap_format(rnp.data(), cnt, hm_off.data(), hm_words.data(), nm.data(), T, nullptr, 0);
+          if (len < 0) die("hit maps: the text could not be formatted");
+          std::string& ht = hm_out[b];
+          ht.resize((size_t)len + 1);
+          if (mic_hitmap_format(rnp.data(), cnt, hm_off.data(), hm_words.data(), nm.data(), T, &ht[0], ht.size()) != len) die("hit maps: the text could not be formatted");
+          ht.resize((size_t)len);
+        }
       } else {
         // every engine of the group probes the same reads against its part of the table - one upload into the first engine, the packed
         // reads fanned out device to device (mic_batch_query_group; the reference uploads the host arrays to every device,
@@ -287,6 +319,16 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
       if (sink_) sink_->append(out[next_write]);
       else if (fout && fwrite(out[next_write].data(), 1, out[next_write].size(), fout) != out[next_write].size() && err.empty()) err = "short write to the result file (disk full?)";
       std::string().swap(out[next_write]);
+      if (mapping()) {
+        std::string& ht = hm_out[next_write];
+        if (sink_) { if (hitmap_sink_) hitmap_sink_->append(ht); }
+        else for (size_t done = 0; done < ht.size() && err.empty();) {
+          const ssize_t w = write(hitmap_fd_, ht.data() + done, ht.size() - done);
+          if (w <= 0) { err = "cannot write " + opt_.hit_maps + " (disk full?)"; break; }
+          done += (size_t)w;
+        }
+        std::string().swap(ht);
+      }
       ++next_write;
     }
     tick(t_write);

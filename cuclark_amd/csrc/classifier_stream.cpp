@@ -219,7 +219,9 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   // --classified-out / --unclassified-out: the two files, created even when they stay empty; the writer puts every batch's split texts
   // at the offsets the batch's turn gives them, like the CSV
   const int split = paired ? 0 : splitting();
-  const bool writing = !summary || split != 0;
+  // --hit-maps: one more file of the same kind - every batch's text behind the header line, at the offset the batch's turn gives it
+  const bool maps = mapping();
+  const bool writing = !summary || split != 0 || maps;
   const std::string* split_name[2] = {&opt_.classified_out, &opt_.unclassified_out};
   int split_fd[2] = {-1, -1};
   for (int c = 0; c < 2; ++c) {
@@ -232,6 +234,21 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
       if (c && split_fd[0] != -1) close(split_fd[0]);
       return true;
     }
+  }
+  int hm_fd = -1;
+  uint64_t hm_off = 0;
+  if (maps) {
+    unlink(opt_.hit_maps.c_str());
+    hm_fd = open(opt_.hit_maps.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    const size_t hl = strlen(MIC_HITMAP_HEADER);
+    if (hm_fd == -1 || pwrite(hm_fd, MIC_HITMAP_HEADER, hl, 0) != (ssize_t)hl) {
+      std::cerr << "Failed to create/open file: " << opt_.hit_maps << std::endl;
+      if (hm_fd != -1) close(hm_fd);
+      if (out_fd != -1) close(out_fd);
+      for (int c = 0; c < 2; ++c) if (split_fd[c] != -1) close(split_fd[c]);
+      return true;
+    }
+    hm_off = hl;
   }
   reset_counts();
   struct timeval t0, t1;
@@ -288,6 +305,8 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
     std::shared_ptr<std::string> own;                                                      // CSV of a host-path batch
     const uint8_t* sp_text[2] = {nullptr, nullptr}; size_t sp_n[2] = {0, 0}; uint64_t sp_off[2] = {0, 0};   // the classified / unclassified records
     std::shared_ptr<std::string> sp_own[2];                                                // ... of a host-path batch
+    const uint8_t* hm_text = nullptr; size_t hm_n = 0; uint64_t hm_off = 0;                // the hit-map text (--hit-maps)
+    std::shared_ptr<std::string> hm_own;                                                   // ... of a host-path batch
     uint64_t ts[6] = {0, 0, 0, 0, 0, 0};   // MIC_CLI_TRACE: slot taken / loaded / device start / device end / write start / write end (us since start)
   };
   const bool trace = getenv("MIC_CLI_TRACE") != nullptr;
@@ -416,6 +435,11 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
               check(mic_ingest_split_text(engines_[eng], slots[it.slot].slot, &it.sp_text[0], &nc, nullptr, &it.sp_text[1], &nu, nullptr), "split text");
               it.sp_n[0] = (size_t)nc; it.sp_n[1] = (size_t)nu;
             }
+            if (maps) {        // a pointer into the slot's pinned hit-map text, made by the batch's own engine: valid until the writer frees the slot
+              uint64_t hb = 0;
+              check(mic_ingest_hitmap_text(engines_[eng], slots[it.slot].slot, &it.hm_text, &hb), "hit-map text");
+              it.hm_n = (size_t)hb;
+            }
           }
           else it.host = true;
         }
@@ -427,12 +451,14 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
           ++n_fallback;
           sink_ = it.own.get();
           for (int c = 0; c < 2; ++c) { it.sp_own[c] = std::make_shared<std::string>(); split_sink_[c] = it.sp_own[c].get(); }
-          try { it.reads = process_segment((const uint8_t*)bytes.data(), bytes.size(), paired, nullptr); } catch (...) { sink_ = nullptr; throw; }
-          sink_ = nullptr;
+          it.hm_own = std::make_shared<std::string>(); hitmap_sink_ = it.hm_own.get();
+          try { it.reads = process_segment((const uint8_t*)bytes.data(), bytes.size(), paired, nullptr); } catch (...) { sink_ = nullptr; hitmap_sink_ = nullptr; throw; }
+          sink_ = nullptr; hitmap_sink_ = nullptr;
+          it.hm_text = (const uint8_t*)it.hm_own->data(); it.hm_n = it.hm_own->size();
           for (int c = 0; c < 2; ++c) { it.sp_text[c] = (const uint8_t*)it.sp_own[c]->data(); it.sp_n[c] = it.sp_own[c]->size(); }
           it.text = it.own->data(); it.text_n = it.own->size();
         }
-      } catch (const std::exception& ex) { fail(ex.what()); it.text_n = 0; it.reads = 0; it.sp_n[0] = it.sp_n[1] = 0; }
+      } catch (const std::exception& ex) { fail(ex.what()); it.text_n = 0; it.reads = 0; it.sp_n[0] = it.sp_n[1] = 0; it.hm_n = 0; }
       it.r.keep.reset();
       if (trace) it.ts[3] = now_us() - t0_us;
       if (timing) { const uint64_t tn = now_us(); us_dev += tn - ta; ts_last_dev = tn; }
@@ -448,6 +474,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
         for (auto f = waiting.find(next_out); f != waiting.end(); f = waiting.find(next_out)) {   // whose turn has come
           f->second.off = out_off; out_off += f->second.text_n; n_objects_ += f->second.reads; ++next_out;
           for (int c = 0; c < 2; ++c) { f->second.sp_off[c] = split_off[c]; split_off[c] += f->second.sp_n[c]; }
+          f->second.hm_off = hm_off; hm_off += f->second.hm_n;
           to_write.push_back(std::move(f->second));
           waiting.erase(f);
         }
@@ -485,6 +512,13 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
           sd += (size_t)n;
         }
       }
+      if (hm_fd != -1) {
+        for (size_t hd = 0; hd < it.hm_n;) {
+          const ssize_t n = pwrite(hm_fd, it.hm_text + hd, it.hm_n - hd, (off_t)(it.hm_off + hd));
+          if (n <= 0) { fail("Failed to write " + opt_.hit_maps + "."); break; }
+          hd += (size_t)n;
+        }
+      }
       if (timing) { const uint64_t tn = now_us(); us_write += tn - ta; ts_last_write = tn; if (tn - ta > us_write_max) us_write_max = tn - ta; }
       if (trace) {
         it.ts[5] = now_us() - t0_us;
@@ -514,6 +548,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   if (prealloc && ftruncate(out_fd, (off_t)out_off) != 0 && err.empty()) err = "Failed to write the results file.";
   if (out_fd != -1) close(out_fd);
   for (int c = 0; c < 2; ++c) if (split_fd[c] != -1 && close(split_fd[c]) != 0 && err.empty()) err = "Failed to write " + *split_name[c] + ".";
+  if (hm_fd != -1 && close(hm_fd) != 0 && err.empty()) err = "Failed to write " + opt_.hit_maps + ".";
   const uint64_t tj2 = now_us();
   release_batches();
   const uint64_t tj3 = now_us();

@@ -67,6 +67,10 @@ static void print_usage(const char* prog) {
                "                     <file>: Name,Reads,Kmers,DistinctKmers,Duplication - many reads over few distinct k-mers (a high duplication) mark\n"
                "                     a low-complexity or contamination artefact; Reads as in --abundance; not with --db-sharded or a list of files;\n"
                "                     works without -R like --abundance\n";
+  std::cout << "--hit-maps <file>,   also write, per object, the runs of k-mer assignments along it into <file>: Object_ID,Hit_map with tokens\n"
+               "                     <target>:<k-mers> (0: no target) joined by blanks, | between two stretches of nucleotides (an N, a masked base, the\n"
+               "                     two mates of -P) - where the hits fall: a chimera reads A:90 0:30 B:70; -O and -P; not with --db-sharded or a\n"
+               "                     list of files; works without -R like --abundance\n";
   std::cout << "--classified-out <file>,  also write the objects that are assigned under --min-confidence / --min-gamma into <file>, as they are in -O\n";
   std::cout << "--unclassified-out <file>,  also write the other objects (no hit, or dropped by the filter) into <file>; either option alone or both;\n"
                "                     one -O input only (not -P, not a list of files); the names are taken as given; work without -R like --abundance\n";
@@ -168,7 +172,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out;
+  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out, hit_maps;
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -220,6 +224,7 @@ int main(int argc, char** argv) {
     if (val == "--unclassified-out") { need("Please specify the file of the unclassified objects!"); unclassified_out = argv[i]; if (unclassified_out.empty()) { std::cerr << "Please specify the file of the unclassified objects!" << std::endl; exit(1); } continue; }
     if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
     if (val == "--kmer-report") { need("Please specify the file of the k-mer report!"); kmer_report = argv[i]; if (kmer_report.empty()) { std::cerr << "Please specify the file of the k-mer report!" << std::endl; exit(1); } continue; }
+    if (val == "--hit-maps") { need("Please specify the file of the hit maps!"); hit_maps = argv[i]; if (hit_maps.empty()) { std::cerr << "Please specify the file of the hit maps!" << std::endl; exit(1); } continue; }
     if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
     if (val == "--lineage") {
       need("Please specify the lineage file!");
@@ -344,6 +349,18 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
+  if (!hit_maps.empty()) {      // refused before any device is touched
+    if (db_sharded) { std::cerr << "--hit-maps does not take --db-sharded: a map is the labels of one GPU's whole table along the object." << std::endl; exit(1); }
+    for (int io : {i_objects, i_objects2})
+      if (io >= 0 && same_file(hit_maps, argv[io])) { std::cerr << "--hit-maps would overwrite the input: " << hit_maps << std::endl; exit(1); }
+    if (i_results >= 0 && same_file(hit_maps, std::string(argv[i_results]) + ".csv")) { std::cerr << "--hit-maps would overwrite the result CSV: " << hit_maps << std::endl; exit(1); }
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out})
+      if (same_file(hit_maps, *f)) { std::cerr << "--hit-maps names the file of another output: " << hit_maps << std::endl; exit(1); }
+    if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
+      std::cerr << "--hit-maps does not take list-of-files mode: classify the files one at a time." << std::endl;
+      exit(1);
+    }
+  }
   if (split) {      // refused before any device is touched
     if (i_objects2 > 0) { std::cerr << "--classified-out / --unclassified-out do not take paired-end input (-P): one -O file only." << std::endl; exit(1); }
     if (same_file(classified_out, unclassified_out)) { std::cerr << "--classified-out and --unclassified-out name the same file: " << classified_out << std::endl; exit(1); }
@@ -356,11 +373,11 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
-  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || split) && i_results < 0 && ext) {
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || !hit_maps.empty() || split) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && !split)) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && hit_maps.empty() && !split)) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -381,6 +398,7 @@ int main(int argc, char** argv) {
   o.rank_report = rank_report; o.lineage = lineage;
   o.density = density;
   o.kmer_report = kmer_report;
+  o.hit_maps = hit_maps;
   o.classified_out = classified_out; o.unclassified_out = unclassified_out;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   o.low_complexity = (uint32_t)lowc;
@@ -407,6 +425,7 @@ int main(int argc, char** argv) {
     }
     if (!classified_out.empty()) std::cout << " - Classified objects stored in " << classified_out << std::endl;
     if (!unclassified_out.empty()) std::cout << " - Unclassified objects stored in " << unclassified_out << std::endl;
+    if (!hit_maps.empty()) std::cout << " - Hit maps stored in " << hit_maps << std::endl;
     if (!density.empty()) {
       const std::vector<uint64_t> counts = classifier->density_counts();
       const std::string report = mic::density::format_report(counts.data());

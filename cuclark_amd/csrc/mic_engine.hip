@@ -176,6 +176,7 @@ struct mic_engine {
   MicDensity density;               // mic_density_*: the engine's counters (mic_density.hip)
   MicSplit split;                   // mic_split_start / _stop: the engine's read-splitting setting (mic_split.hip)
   MicKsketch ksketch;               // mic_ksketch_*: the engine's k-mer sketches (mic_ksketch.hip)
+  MicHitmap hitmap;                 // mic_hitmap_start / _stop: the engine's hit-map setting (mic_hitmap.hip)
 };
 
 namespace {
@@ -619,6 +620,7 @@ MicRollup* mic_engine_rollup(mic_engine* e) { return &e->rollup; }
 MicDensity* mic_engine_density(mic_engine* e) { return &e->density; }
 MicSplit* mic_engine_split(mic_engine* e) { return &e->split; }
 MicKsketch* mic_engine_ksketch(mic_engine* e) { return &e->ksketch; }
+MicHitmap* mic_engine_hitmap(mic_engine* e) { return &e->hitmap; }
 uint32_t mic_engine_row_words(const mic_engine* e) { return e->cfg.row_words; }
 hipStream_t mic_engine_stream(mic_engine* e) { return e->stream; }
 void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down) { *up = e->up_stream; *down = e->down_stream; }
@@ -1069,6 +1071,38 @@ int mic_batch_ksketch(mic_engine* e, size_t batch) {
   HIPTRY(mic_launch_ksketch(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, B.n_reads, B.d_results, ks.n_targets, ks.d_regs, ks.d_hits,
                             nullptr, B.stream));
   HIPTRY(hipStreamSynchronize(B.stream));
+  return MIC_OK;
+}
+
+// the hit maps of the batch's reads (mic_hitmap.h) into host arrays: the kernels of mic_hitmap_device on the batch's device-resident
+// packed reads and results; a first run sizes, a second fills when the caller's words hold the total
+int mic_batch_hitmap(mic_engine* e, size_t batch, uint32_t* offsets, size_t off_cap, uint32_t* words, size_t cap_words, uint64_t* n_words) {
+  if (!e || batch >= e->batches.size() || !n_words) return fail(MIC_E_INVALID, "bad argument");
+  Batch& B = e->batches[batch];
+  if (!B.scheduled) return fail(MIC_E_STATE, "batch %zu was not queried", batch);
+  if (e->table.sharded || e->table.parted) return fail(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
+  int rc = set_device(e);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(e->submit_mu);
+  HIPTRY(hipEventSynchronize(B.done));
+  const size_t n = B.n_reads;
+  uint32_t* d_off = nullptr; uint32_t* d_words = nullptr;
+  *n_words = 0;
+  HIPTRY(hipMalloc(&d_off, (n + 1) * 4));
+  uint64_t total = 0;
+  rc = mic_hitmap_run(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, n, B.d_results, e->cfg.num_targets, d_off, nullptr, 0, &total, B.stream);
+  hipError_t he = hipSuccess;
+  if (!rc && words && total && total <= cap_words) {
+    he = hipMalloc(&d_words, total * 4);
+    if (he == hipSuccess) rc = mic_hitmap_run(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, n, B.d_results, e->cfg.num_targets, d_off, d_words, total, &total, B.stream);
+    if (he == hipSuccess && !rc) he = hipMemcpy(words, d_words, total * 4, hipMemcpyDeviceToHost);
+  }
+  if (he == hipSuccess && !rc && offsets && off_cap >= n + 1) he = hipMemcpy(offsets, d_off, (n + 1) * 4, hipMemcpyDeviceToHost);
+  hipFree(d_off);
+  if (d_words) hipFree(d_words);
+  if (rc) return rc;
+  if (he != hipSuccess) return fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "hit maps of a batch: %s", hipGetErrorString(he));
+  *n_words = total;
   return MIC_OK;
 }
 

@@ -654,3 +654,63 @@ extern "C" int mic_split_host(const uint8_t* text, size_t nb, const uint64_t* re
   auto rule = [&](size_t r) { return mic_split_classified(results + r * MIC_RESULT_WORDS, norm ? norm[r] : 0u, k, n_targets, *filter); };
   return mic_split_partition_host(text, nb, rec_start, n_reads, which, rule, out, totals) ? MIC_OK : MIC_E_INVALID;
 }
+
+// ---- hit maps: the rule of mic_hitmap.h on the CPU - the run-length encoding of the labels along a read, and the text ----------------
+#include "mic_hitmap.h"
+
+extern "C" {
+long mic_hitmap_runs_host(const uint32_t* labels, const uint32_t* part_nk, size_t n_parts, uint32_t n_targets, uint32_t* words, size_t cap) {
+  if (n_parts && !part_nk) return MIC_E_INVALID;
+  size_t n = 0, at = 0;
+  auto put = [&](uint32_t w) { if (words && n < cap) words[n] = w; ++n; };
+  bool first = true;
+  for (size_t p = 0; p < n_parts; ++p) {
+    const uint32_t nk = part_nk[p];
+    if (nk == 0) continue;
+    if (nk > 0xFFFFu || !labels) return MIC_E_INVALID;
+    if (!first) put(MIC_HITMAP_SEP);
+    first = false;
+    uint32_t cl = mic_hitmap_label(labels[at], true, n_targets), clen = 1;
+    for (uint32_t i = 1; i < nk; ++i) {
+      const uint32_t l = mic_hitmap_label(labels[at + i], true, n_targets);
+      if (l == cl) { ++clen; continue; }
+      put(mic_hitmap_word(cl, clen));
+      cl = l; clen = 1;
+    }
+    put(mic_hitmap_word(cl, clen));
+    at += nk;
+  }
+  return (long)n;
+}
+
+long mic_hitmap_format(const char* const* read_names, size_t n_reads, const uint32_t* offsets, const uint32_t* words,
+                       const char* const* target_names, uint32_t n_targets, char* buf, size_t cap) {
+  if (n_reads && (!read_names || !offsets)) return MIC_E_INVALID;
+  if (n_targets && !target_names) return MIC_E_INVALID;
+  for (uint32_t t = 0; t < n_targets; ++t) if (!target_names[t]) return MIC_E_INVALID;
+  std::string text;
+  char num[16];
+  for (size_t r = 0; r < n_reads; ++r) {
+    if (!read_names[r] || offsets[r + 1] < offsets[r] || (offsets[r + 1] > offsets[r] && !words)) return MIC_E_INVALID;
+    size_t nl = strlen(read_names[r]);
+    if (nl >= 40) nl = MIC_HITMAP_NAME_MAX;
+    text.append(read_names[r], nl);
+    text += ',';
+    for (uint32_t i = offsets[r]; i < offsets[r + 1]; ++i) {
+      const uint32_t w = words[i];
+      if (i != offsets[r]) text += ' ';
+      if (w == MIC_HITMAP_SEP) { text += '|'; continue; }
+      const uint32_t l = mic_hitmap_word_label(w);
+      if (l == 0) text += '0';
+      else if (l > n_targets) text += "NA";
+      else text += target_names[l - 1];
+      text += ':';
+      snprintf(num, sizeof(num), "%u", mic_hitmap_word_len(w));
+      text += num;
+    }
+    text += '\n';
+  }
+  if (buf && text.size() < cap) memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
+}
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include "mic_fmt.h"
 #include "mic_qmask.h"
 #include "mic_lowc.h"
+#include "mic_hitmap.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -42,6 +43,7 @@ MicRollup* mic_engine_rollup(mic_engine* e);
 MicDensity* mic_engine_density(mic_engine* e);
 MicKsketch* mic_engine_ksketch(mic_engine* e);
 MicSplit* mic_engine_split(mic_engine* e);
+MicHitmap* mic_engine_hitmap(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
 uint32_t* mic_engine_low_complexity(mic_engine* e);
 void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
@@ -475,6 +477,53 @@ __global__ void __launch_bounds__(256) nocsv_status_kernel(const uint32_t* __res
   }
 }
 
+// ---- hit-map text (mic_hitmap.h: "<name>,<tokens joined by spaces>\n") - csv_len_kernel / csv_fmt_kernel's pattern: one thread per
+// read computes its line's length from the name, the words and the target-name offsets, a 64-bit exclusive sum gives the lines'
+// places, one thread per read writes its line.  No cap on a line's length and no hand-back: a long read's line is as long as its map.
+struct HitmapTextArgs {
+  const uint8_t* raw; const uint32_t* name_s; const uint8_t* name_len;
+  const uint32_t* offsets; const uint32_t* words;
+  const char* tnames; const uint32_t* tname_off; uint32_t n_targets, n_reads;
+};
+
+__global__ void __launch_bounds__(256) hitmap_len_kernel(HitmapTextArgs a, unsigned long long* __restrict__ line_len) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r > a.n_reads) return;
+  if (r == a.n_reads) { line_len[r] = 0; return; }
+  uint32_t nl = a.name_len[r]; if (nl >= 40) nl = MIC_HITMAP_NAME_MAX;
+  const uint32_t w0 = a.offsets[r], w1 = a.offsets[r + 1];
+  unsigned long long ll = (unsigned long long)nl + 2u + (w1 > w0 ? w1 - w0 - 1u : 0u);      // name , tokens' spaces \n
+  for (uint32_t i = w0; i < w1; ++i) {
+    const uint32_t w = a.words[i], l = mic_hitmap_word_label(w);
+    ll += w == MIC_HITMAP_SEP ? 1u : (l == 0 ? 1u : l > a.n_targets ? 2u : a.tname_off[l] - a.tname_off[l - 1]) + 1u + digits_u32(mic_hitmap_word_len(w));
+  }
+  line_len[r] = ll;
+}
+
+__global__ void __launch_bounds__(256) hitmap_fmt_kernel(HitmapTextArgs a, const unsigned long long* __restrict__ line_off, char* __restrict__ out) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= a.n_reads) return;
+  uint32_t nl = a.name_len[r]; if (nl >= 40) nl = MIC_HITMAP_NAME_MAX;
+  char* p = out + line_off[r];
+  const uint8_t* nm = a.raw + a.name_s[r];
+  for (uint32_t i = 0; i < nl; ++i) *p++ = (char)nm[i];
+  *p++ = ',';
+  char tmp[16];
+  const uint32_t w0 = a.offsets[r], w1 = a.offsets[r + 1];
+  for (uint32_t i = w0; i < w1; ++i) {
+    const uint32_t w = a.words[i], l = mic_hitmap_word_label(w);
+    if (i != w0) *p++ = ' ';
+    if (w == MIC_HITMAP_SEP) { *p++ = '|'; continue; }
+    if (l == 0) *p++ = '0';
+    else if (l > a.n_targets) { *p++ = 'N'; *p++ = 'A'; }
+    else { const char* t = a.tnames + a.tname_off[l - 1]; const uint32_t tl = a.tname_off[l] - a.tname_off[l - 1]; for (uint32_t j = 0; j < tl; ++j) *p++ = t[j]; }
+    *p++ = ':';
+    const int n = mic_fmt_u32(mic_hitmap_word_len(w), tmp);
+    for (int j = 0; j < n; ++j) *p++ = tmp[j];
+  }
+  *p++ = '\n';
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 // ---- a pair of FASTQ texts resident on the device (the inflated mates of -P a.fq.gz b.fq.gz): line index, checks, merge --------------
 // The reference merges a pair line by line into ">id\nseq1Nseq2\n" (file.cc:205-268); the command line's loaders do that on the
@@ -630,6 +679,16 @@ struct Slot {
   uint8_t* d_split = nullptr; uint8_t* h_split = nullptr; uint64_t* h_split_tot = nullptr;
   MicSplitBufs split_b;
   int split_which = 0; bool split_valid = false;
+  // hit maps (mic_hitmap_start on the slot's engine; allocated with the slots when started by then, else with the first such batch):
+  // counts / offsets (u32) and line lengths / line offsets (u64) of max_reads + 2 items each with the two scans' storage in one allocation;
+  // the word buffer, the text buffer and its pinned twin are allocations of their own that grow when a batch needs more and never shrink;
+  // {words, text bytes} of the last batch in pinned memory
+  uint32_t* d_hm_cnt = nullptr; uint32_t* d_hm_off = nullptr; unsigned long long* d_hm_len = nullptr; unsigned long long* d_hm_loff = nullptr;
+  void* d_hm_tmp = nullptr; size_t hm_tmp_bytes = 0;
+  uint32_t* d_hm_words = nullptr; size_t hm_words_cap = 0;
+  char* d_hm_text = nullptr; char* h_hm_text = nullptr; size_t hm_text_cap = 0;
+  uint64_t* h_hm_tot = nullptr;
+  bool hm_valid = false;
   // table-sharded batches (mic_ingest_classify_group): what this slot keeps on every engine of its group, the owner included
   struct Peer {
     mic_engine* eng = nullptr; int device = 0;
@@ -782,6 +841,9 @@ void free_ingest(Ingest* g) {
     hipSetDevice(g->device);
     for (void* p : s.dev_allocs) hipFree(p);
     for (void* p : s.host_allocs) hipHostFree(p);
+    if (s.d_hm_words) hipFree(s.d_hm_words);
+    if (s.d_hm_text) hipFree(s.d_hm_text);
+    if (s.h_hm_text) hipHostFree(s.h_hm_text);
     if (s.ev) mic_event_put(s.ev);
     if (s.ev_up) mic_event_put(s.ev_up);
     if (s.ev_k) mic_event_put(s.ev_k);
@@ -837,6 +899,65 @@ int ensure_split_buffers(Ingest* g, Slot& s) {
   s.split_b.d_ncls = (uint32_t*)(q + text + 2 * arr); s.split_b.d_tmp = q + text + 2 * arr + 256; s.split_b.tmp_bytes = tmp;
   s.h_split = (uint8_t*)h; s.h_split_tot = (uint64_t*)((char*)h + text);
   s.d_split = (uint8_t*)d;
+  return MIC_OK;
+}
+
+// the slot's hit-map buffers: the fixed arrays once; the word buffer for at least `words` words and the text buffer (with its pinned
+// twin) for at least `text` bytes - grown, never shrunk; what they held is not kept (the caller grows them before the pass that fills them)
+size_t hitmap_scan64_bytes(size_t n_items) {
+  size_t tb = 0;
+  hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n_items);
+  return tb + 256;
+}
+int ensure_hitmap_buffers(Ingest* g, Slot& s, size_t words, size_t text) {
+  hipError_t e;
+  if (!s.d_hm_cnt) {
+    const size_t n = g->max_reads + 2;
+    const size_t a32 = (n * 4 + 255) & ~(size_t)255, a64 = (n * 8 + 255) & ~(size_t)255;
+    const size_t tmp = std::max(mic_hitmap_tmp_bytes(n), hitmap_scan64_bytes(n));
+    void* d = nullptr; void* h = nullptr;
+    e = hipHostMalloc(&h, 64, hipHostMallocDefault);
+    if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: pinned memory for the hit maps' totals: %s", hipGetErrorString(e));
+    memset(h, 0, 64);
+    e = hipMalloc(&d, 2 * a32 + 2 * a64 + tmp);
+    if (e != hipSuccess) {
+      hipHostFree(h);
+      return mic_set_error(MIC_E_NOMEM, "ingest slot: hit-map arrays of %zu bytes: %s", 2 * a32 + 2 * a64 + tmp, hipGetErrorString(e));
+    }
+    s.host_allocs.push_back(h);
+    s.dev_allocs.push_back(d);
+    char* q = (char*)d;
+    s.d_hm_len = (unsigned long long*)q; s.d_hm_loff = (unsigned long long*)(q + a64);
+    s.d_hm_cnt = (uint32_t*)(q + 2 * a64); s.d_hm_off = (uint32_t*)(q + 2 * a64 + a32);
+    s.d_hm_tmp = q + 2 * a64 + 2 * a32; s.hm_tmp_bytes = tmp;
+    s.h_hm_tot = (uint64_t*)h;
+    // first sizes: a word per 64 bytes of the slot's text (a 150-nt read without its quality line is ~165 bytes and a few runs), a
+    // quarter of its bytes of text (a name, a comma and ~10 bytes per run); a batch of denser maps grows them once
+    words = std::max(words, g->max_bytes / 64);
+    text = std::max(text, g->max_bytes / 4);
+  }
+  if (words > s.hm_words_cap) {
+    const size_t cap = std::max(words + words / 2, (size_t)1024);
+    if (s.d_hm_words) { hipFree(s.d_hm_words); s.d_hm_words = nullptr; s.hm_words_cap = 0; }
+    void* d = nullptr;
+    e = hipMalloc(&d, cap * 4);
+    if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu hit-map words: %s", cap, hipGetErrorString(e));
+    s.d_hm_words = (uint32_t*)d; s.hm_words_cap = cap;
+  }
+  if (text > s.hm_text_cap) {
+    const size_t cap = (std::max(text + text / 4, (size_t)4096) + 255) & ~(size_t)255;
+    if (s.d_hm_text) { hipFree(s.d_hm_text); s.d_hm_text = nullptr; }
+    if (s.h_hm_text) { hipHostFree(s.h_hm_text); s.h_hm_text = nullptr; }
+    s.hm_text_cap = 0;
+    void* d = nullptr; void* h = nullptr;
+    mic_bind_thread_near_device(g->device, 1);
+    e = hipHostMalloc(&h, cap, hipHostMallocDefault);
+    mic_bind_thread_near_device(g->device, 0);
+    if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu bytes of pinned memory for the hit-map text: %s", cap, hipGetErrorString(e));
+    e = hipMalloc(&d, cap);
+    if (e != hipSuccess) { hipHostFree(h); return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu bytes of hit-map text: %s", cap, hipGetErrorString(e)); }
+    s.d_hm_text = (char*)d; s.h_hm_text = (char*)h; s.hm_text_cap = cap;
+  }
   return MIC_OK;
 }
 
@@ -1158,11 +1279,12 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
     std::vector<std::string> msgs(n_slots);
     std::vector<std::thread> th;
     // (read splitting already started on the engine: the slots' split buffers come now, pinned side by side, not with the first batches)
-    const bool split_now = mic_engine_split(e)->on;
+    const bool split_now = mic_engine_split(e)->on, hitmap_now = mic_engine_hitmap(e)->on;
     for (size_t i = 0; i < n_slots; ++i)
       th.emplace_back([&, i] {
         rcs[i] = alloc_slot(g, g->slots[i], tmp, dev);
         if (!rcs[i] && split_now) rcs[i] = ensure_split_buffers(g, g->slots[i]);
+        if (!rcs[i] && hitmap_now) rcs[i] = ensure_hitmap_buffers(g, g->slots[i], 0, 0);
         if (rcs[i]) msgs[i] = mic_last_error();
       });
     for (auto& t : th) t.join();
@@ -1193,6 +1315,9 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   // k-mer sketches count the k-mers of ONE engine's table behind ITS query: the table-sharded mode is not integrated
   if (n_group > 1) for (size_t p = 0; p < n_group; ++p) if (mic_engine_ksketch(group[p])->on)
     return mic_set_error(MIC_E_UNSUPPORTED, "k-mer sketches are started on an engine of a table-sharded group: not supported");
+  // hit maps are the labels of ONE engine's table along the read: likewise
+  if (n_group > 1) for (size_t p = 0; p < n_group; ++p) if (mic_engine_hitmap(group[p])->on)
+    return mic_set_error(MIC_E_UNSUPPORTED, "hit maps are started on an engine of a table-sharded group: not supported");
   const int paired = flags & MIC_INGEST_PAIRED;
   const bool no_csv = (flags & MIC_INGEST_NO_CSV) != 0;
   const uint32_t lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;      // lines per FASTQ record
@@ -1213,7 +1338,9 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
   ITRY(hipSetDevice(dev));
   Slot& s = g->slots[slot_id];
-  s.ru_valid = false; s.split_valid = false;
+  s.ru_valid = false; s.split_valid = false; s.hm_valid = false;
+  const bool hitmaps = mic_engine_hitmap(e)->on;
+  if (hitmaps && (t.sharded || t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
   memset(out, 0, sizeof(*out));
   const bool resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
   const uint8_t first = resident ? (uint8_t)((flags & MIC_INGEST_RESIDENT_FASTQ) == MIC_INGEST_RESIDENT_FASTQ ? '@' : '>') : s.h_raw[0];
@@ -1365,6 +1492,42 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     }
     s.split_which = sp.which; s.split_valid = true;
   }
+  if (hitmaps) {
+    // hit maps (mic_hitmap_start on the slot's engine), behind the status check like the split: words per read, their exclusive sum,
+    // the words; line lengths, their exclusive sum, the lines.  The host reads the word total and later the text total (8 bytes
+    // each) and grows the buffer that is too small before the pass that fills it.
+    if ((rc = ensure_hitmap_buffers(g, s, 0, 0))) return rc;
+    ITRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, nullptr, s.d_hm_cnt, false, st));
+    ITRY(mic_hitmap_scan(s.d_hm_tmp, s.hm_tmp_bytes, s.d_hm_cnt, s.d_hm_off, (size_t)n_reads + 1, st));
+    s.h_hm_tot[0] = 0;
+    ITRY(hipMemcpyAsync(s.h_hm_tot, s.d_hm_off + n_reads, 4, hipMemcpyDeviceToHost, st));
+    ITRY(hipEventRecord(s.ev, st));
+    ITRY(wait_event(s.ev));
+    const size_t n_words = (size_t)s.h_hm_tot[0];
+    if ((rc = ensure_hitmap_buffers(g, s, n_words, 0))) return rc;
+    ITRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, s.d_hm_off, s.d_hm_words, true, st));
+    HitmapTextArgs ha;
+    ha.raw = s.d_raw; ha.name_s = s.rec.name_s; ha.name_len = s.rec.name_len; ha.offsets = s.d_hm_off; ha.words = s.d_hm_words;
+    ha.tnames = g->d_tnames; ha.tname_off = g->d_tname_off; ha.n_targets = g->n_targets; ha.n_reads = n_reads;
+    hitmap_len_kernel<<<gr, 256, 0, st>>>(ha, s.d_hm_len);
+    tb = s.hm_tmp_bytes;
+    ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_hm_tmp, tb, s.d_hm_len, s.d_hm_loff, (int)(n_reads + 1), st));
+    ITRY(hipMemcpyAsync(s.h_hm_tot + 1, s.d_hm_loff + n_reads, 8, hipMemcpyDeviceToHost, st));
+    ITRY(hipEventRecord(s.ev, st));
+    ITRY(wait_event(s.ev));
+    const size_t n_text = (size_t)s.h_hm_tot[1];
+    if ((rc = ensure_hitmap_buffers(g, s, 0, n_text))) return rc;
+    hitmap_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ha, s.d_hm_loff, s.d_hm_text);
+    ITRY(hipGetLastError());
+    ITRY(hipEventRecord(s.ev_k, st));
+    ITRY(hipStreamWaitEvent(down, s.ev_k, 0));
+    ITRY(hipMemcpyAsync(s.h_hm_text, s.d_hm_text, n_text, hipMemcpyDeviceToHost, down));
+    if (no_csv) {      // (with a CSV, phase 3's wait for the download stream covers this copy)
+      ITRY(hipEventRecord(s.ev, down));
+      ITRY(wait_event(s.ev));
+    }
+    s.hm_valid = true;
+  }
   if (no_csv) {
     out->n_reads = n_reads; out->csv_bytes = 0; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
     out->status = MIC_INGEST_OK;
@@ -1430,6 +1593,16 @@ int mic_ingest_split_text(mic_engine* e, size_t slot_id, const uint8_t** classif
   if (unclassified) *unclassified = wu ? s.h_split + a : nullptr;
   if (unclassified_bytes) *unclassified_bytes = wu ? b : 0;
   if (n_unclassified) *n_unclassified = s.n_reads - nc;
+  return MIC_OK;
+}
+
+int mic_ingest_hitmap_text(mic_engine* e, size_t slot_id, const uint8_t** text, uint64_t* bytes) {
+  if (!e || !text || !bytes) return mic_set_error(MIC_E_INVALID, "null argument");
+  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
+  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  const Slot& s = g->slots[slot_id];
+  if (!s.hm_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no hit-map text (mic_hitmap_start, MIC_INGEST_OK)");
+  *text = (const uint8_t*)s.h_hm_text; *bytes = s.h_hm_tot[1];
   return MIC_OK;
 }
 

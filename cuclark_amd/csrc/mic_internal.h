@@ -255,6 +255,23 @@ hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const
                               const uint32_t* results, uint32_t n_targets, uint8_t* regs, unsigned long long* hits, const uint32_t* status,
                               hipStream_t s);
 
+// ---- hit maps (mic_hitmap.hip; the kernel: mic_kernels.hip; the text kernels: mic_ingest.hip; the rule: mic_hitmap.h) ----------------
+// An engine's setting while mic_hitmap_start is in force: every ingest batch it owns that returns MIC_INGEST_OK gets its map and text.
+struct MicHitmap {
+  bool on = false;
+};
+// one pass of hitmap_kernel over reads [0, n_reads): fill == false: out = n_reads + 1 word counts (item n_reads = 0), offsets unused;
+// fill == true: out = the words, offsets = the exclusive sum of the counts (n_reads + 1).  n_cu caps the grid.
+hipError_t mic_launch_hitmap(const MicTable& t, int slot_class, int n_cu, const uint32_t* reads_ptr, const uint16_t* cont, size_t n_reads,
+                             const uint32_t* results, uint32_t n_targets, const uint32_t* offsets, uint32_t* out, bool fill, hipStream_t s);
+// the scan between the passes: its temporary storage for n_items u32, and the scan itself (counts -> offsets)
+size_t mic_hitmap_tmp_bytes(size_t n_items);
+hipError_t mic_hitmap_scan(void* d_tmp, size_t tmp_bytes, const uint32_t* counts, uint32_t* offsets, size_t n_items, hipStream_t s);
+// count, scan, word total to the host, fill when the words fit cap_words (mic_hitmap_device's contract) on device arrays; synchronous
+int mic_hitmap_run(const MicTable& t, int slot_class, int n_cu, const uint32_t* d_rp, const uint16_t* d_cont, size_t n_reads,
+                   const uint32_t* d_results, uint32_t n_targets, uint32_t* d_offsets, uint32_t* d_words, size_t cap_words, uint64_t* n_words,
+                   hipStream_t s);
+
 // ---- read splitting (mic_split.hip; the rule: mic_split.h) --------------------------------------------------------------------------
 // An engine's setting while mic_split_start is in force: every ingest batch it owns that returns MIC_INGEST_OK is partitioned.
 struct MicSplit {

@@ -14,6 +14,7 @@
 #include "mic_internal.h"
 #include "mic_device.h"
 #include "mic_ksketch.h"
+#include "mic_hitmap.h"
 #include "mic_join2.h"      // query_kernel_r: a read of two parts as one joined window, and its host model
 
 #include <stdlib.h>
@@ -2159,7 +2160,111 @@ __global__ void __launch_bounds__(256) ksketch_kernel(const MicTable t, const ui
   }
 }
 
+// ---- hit maps (mic_hitmap.h: the rule): per read, the runs of equal labels along its k-mer positions ------------------------------
+// ksketch_kernel's shape: a scalar probe pass behind the query, one wavefront per read on a capped grid whose waves stride over the
+// batch, rounds of 64 positions with a trip count that is uniform in the wave.  Per round each lane probes its position and starts a
+// run when its label differs from its left neighbour's (one cross-lane shift; lane 0 compares against the label the previous round
+// ended with).  The ballot of the starts is the round: its popcount is the number of runs that begin in it, the popcount below a
+// start lane is that run's word index, the distance to the next start bit its length.  The run that is still open at the end of a
+// round is carried in wave-uniform registers (label, length so far) and written once, by lane 0, when a later start closes it or at
+// the part's end - no lane ever patches a word in memory.
+//   FILL = false   the read's word count only (out[r]); an exclusive sum over n_reads + 1 items then gives the offsets
+//   FILL = true    the words at out + offsets[r]; a store at or behind offsets[r + 1] is dropped (the two passes compute the same
+//                  map from the same inputs: the guard only keeps a caller's mistake inside the caller's buffer)
+// A read whose result row has sum 0 is not probed: its map is 0:nk per part, straight from the part headers.
+// No LDS, no atomics: plain vector loads and stores.
+template <bool KEY64, bool FILL>
+__global__ void __launch_bounds__(256) hitmap_kernel(const MicTable t, const uint32_t* __restrict__ reads_ptr,
+                                                     const uint16_t* __restrict__ cont, uint32_t n_reads,
+                                                     const uint32_t* __restrict__ results, uint32_t n_targets,
+                                                     const uint32_t* __restrict__ offsets, uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int k = t.k;
+  const uint64_t n_waves = (uint64_t)gridDim.x * 4;
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) out[n_reads] = 0;       // the scan's last item
+  for (uint64_t r = (uint64_t)blockIdx.x * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); r < n_reads; r += n_waves) {
+    const bool probed = results[r * MIC_RESULT_WORDS] != 0;    // uniform in the wave
+    uint32_t pp = reads_ptr[r];
+    const uint32_t pe = reads_ptr[r + 1];
+    uint32_t nw = 0;                                           // words so far (uniform)
+    uint32_t wbase = 0, wend = 0;
+    if (FILL) { wbase = offsets[r]; wend = offsets[r + 1]; }
+    uint32_t* __restrict__ w = out + wbase;
+    const uint32_t wcap = wend - wbase;
+#define HM_PUT(idx_, word_) do { if (FILL && (idx_) < wcap) w[(idx_)] = (word_); } while (0)
+    bool first_part = true;
+    while (pp < pe) {
+      const uint32_t plen = cont[pp];
+      if (plen == 0) break;
+      const uint32_t first = pp + 1;
+      pp = first + (plen + 7) / 8;
+      if (plen < (uint32_t)k) continue;
+      const uint32_t nk = plen - k + 1;
+      if (!first_part) { if (lane == 0) HM_PUT(nw, MIC_HITMAP_SEP); ++nw; }
+      first_part = false;
+      if (!probed) { if (lane == 0) HM_PUT(nw, mic_hitmap_word(0u, nk)); ++nw; continue; }
+      uint32_t cl = 0, clen = 0;                               // the open run: its label, its length so far (0: none is open)
+      for (uint32_t base = 0; base < nk; base += 64) {         // uniform trip count: the ballot below sees the whole wave
+        const uint32_t pos = base + lane;
+        const uint32_t nvalid = nk - base < 64u ? nk - base : 64u;
+        uint32_t lab = 0;
+        if (pos < nk) {
+          // nucleotides [pos, pos+k): containers pos/8 .. (pos+k-1)/8, at most 5
+          const uint32_t c0 = first + pos / 8;
+          uint64_t hi = 0; uint32_t lo = 0;  // 80-bit window hi(64) : lo(16)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hi = (hi << 16) | (c0 + i < pp ? cont[c0 + i] : 0);
+          lo = c0 + 4 < pp ? cont[c0 + 4] : 0;
+          const int s = 2 * (pos & 7);
+          const uint64_t x = s ? ((hi << s) | ((uint64_t)lo >> (16 - s))) : hi;
+          const uint64_t kmer = x >> (64 - 2 * k);
+          bool mine = true;
+          const uint32_t m = probe_any<KEY64>(t, kmer, pos, &mine);
+          lab = mic_hitmap_label(m, mine, n_targets);
+        }
+        const uint32_t left = __shfl_up(lab, 1);
+        const bool start = pos < nk && (lane == 0 ? (clen == 0 || lab != cl) : lab != left);
+        const uint64_t starts = wballot(start);
+        if (starts == 0) { clen += nvalid; continue; }         // the whole round continues the open run
+        const uint32_t f = (uint32_t)__builtin_ctzll(starts), last = 63u - (uint32_t)__builtin_clzll(starts);
+        if (clen) { if (lane == 0) HM_PUT(nw, mic_hitmap_word(cl, clen + f)); ++nw; }
+        if (FILL && start && (uint32_t)lane != last) {         // a run that begins and ends in this round: a higher start bit exists
+          const uint32_t idx = nw + (uint32_t)__builtin_popcountll(starts & ((1ull << lane) - 1ull));
+          const uint32_t len = 1u + (uint32_t)__builtin_ctzll((starts >> 1) >> lane);
+          HM_PUT(idx, mic_hitmap_word(lab, len));
+        }
+        nw += (uint32_t)__builtin_popcountll(starts) - 1u;
+        cl = __builtin_amdgcn_readlane(lab, last);
+        clen = nvalid - last;
+      }
+      if (clen) { if (lane == 0) HM_PUT(nw, mic_hitmap_word(cl, clen)); ++nw; }
+    }
+#undef HM_PUT
+    if (!FILL && lane == 0) out[r] = nw;
+  }
+}
+
 }  // namespace
+
+// the two passes of a batch's hit maps (mic_internal.h): counts = n_reads + 1 u32 (item n_reads = 0), then - behind an exclusive sum of
+// them - the words
+hipError_t mic_launch_hitmap(const MicTable& t, int slot_class, int n_cu, const uint32_t* reads_ptr, const uint16_t* cont, size_t n_reads,
+                             const uint32_t* results, uint32_t n_targets, const uint32_t* offsets, uint32_t* out, bool fill, hipStream_t s) {
+  if (!n_reads) return hipSuccess;
+  // the grid of mic_launch_ksketch: four reads per block, at most 64 blocks per CU, whose waves then stride over the batch
+  size_t blocks = (n_reads + 3) / 4;
+  const size_t cap = (size_t)(n_cu > 0 ? n_cu : 256) * 64;
+  if (blocks > cap) blocks = cap;
+  const uint32_t n = (uint32_t)n_reads;
+  if (slot_class == 64) {
+    if (fill) hitmap_kernel<true, true><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, n, results, n_targets, offsets, out);
+    else hitmap_kernel<true, false><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, n, results, n_targets, nullptr, out);
+  } else {
+    if (fill) hitmap_kernel<false, true><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, n, results, n_targets, offsets, out);
+    else hitmap_kernel<false, false><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, n, results, n_targets, nullptr, out);
+  }
+  return hipGetLastError();
+}
 
 hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const uint32_t* reads_ptr, const uint16_t* cont, size_t n_reads,
                               const uint32_t* results, uint32_t n_targets, uint8_t* regs, unsigned long long* hits, const uint32_t* status,

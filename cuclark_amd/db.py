@@ -500,6 +500,39 @@ class MiClarkDB:
                                       tot.ctypes.data, stream or None))
         return tuple(int(x) for x in tot)
 
+    # -- hit maps (mic_hitmap_*): per read the runs of k-mer assignments along it: offsets u32[n + 1], words u32 (csrc/mic_hitmap.h)
+    def hitmap_device(self, d_reads_pointer, d_containers, n_reads, d_results, d_offsets, d_words=0, cap_words=0, stream=0):
+        """The kernels alone on caller-owned device memory (packed reads and result rows as for query_device): fills d_offsets
+        (u32[n_reads + 1]) and returns the number of words; d_words (u32[cap_words]) is filled only when cap_words holds them all.
+        Synchronous."""
+        n = C.c_uint64(0)
+        check(self.L.mic_hitmap_device(self.h, d_reads_pointer, d_containers, n_reads, d_results, d_offsets, d_words or None, cap_words,
+                                       C.byref(n), stream or None))
+        return int(n.value)
+
+    def hitmap_start(self):
+        """From now on every ingest batch of this engine that returns MIC_INGEST_OK gets its hit maps and their text."""
+        check(self.L.mic_hitmap_start(self.h))
+
+    def hitmap_stop(self):
+        check(self.L.mic_hitmap_stop(self.h))
+
+    def ingest_hitmap_text(self, slot):
+        """bytes: the hit-map text (no header line) of the slot's last batch; MicError (MIC_E_STATE) when it left none."""
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        check(self.L.mic_ingest_hitmap_text(self.h, slot, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def batch_hitmap(self, batch, n_reads):
+        """(offsets u32[n_reads + 1], words u32) of a batch of the batch API (after its wait; n_reads as given to readyBatch): sized
+        with one call, filled with a second."""
+        n = C.c_uint64(0)
+        off = np.zeros(int(n_reads) + 1, np.uint32)
+        check(self.L.mic_batch_hitmap(self.h, batch, off.ctypes.data, off.size, None, 0, C.byref(n)))
+        words = np.zeros(max(int(n.value), 1), np.uint32)
+        check(self.L.mic_batch_hitmap(self.h, batch, off.ctypes.data, off.size, words.ctypes.data, words.size, C.byref(n)))
+        return off, words[: int(n.value)]
+
     def ingest_fetch_group_rows(self, slot, part):
         """test hook: the partial rows engine `part` of the group computed for the slot's last table-sharded batch"""
         n, rw = C.c_uint64(0), C.c_uint32(0)

@@ -244,6 +244,42 @@ def ksketch_report(names, reads, regs, hits):
     return buf.raw[:ln].decode()
 
 
+def hitmap_runs(labels, part_nk, n_targets):
+    """mic_hitmap_runs_host: the hit-map rule of csrc/mic_hitmap.h on the labels of one read's k-mer positions, part after part (label 0
+    or above n_targets: no target); part_nk: positions per part.  Returns the words (u32): (label << 16) | len per run, 0 between parts."""
+    L = _lib.load()
+    lb = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+    nk = np.ascontiguousarray(part_nk, np.uint32).reshape(-1)
+    assert int(nk.astype(np.int64).sum()) == lb.size, "one label per k-mer position"
+    args = (lb.ctypes.data if lb.size else None, nk.ctypes.data if nk.size else None, nk.size, int(n_targets))
+    n = L.mic_hitmap_runs_host(*args, None, 0)
+    if n < 0:
+        raise ValueError(f"mic_hitmap_runs_host: invalid argument ({n})")
+    words = np.zeros(max(n, 1), np.uint32)
+    assert L.mic_hitmap_runs_host(*args, words.ctypes.data, words.size) == n
+    return words[:n]
+
+
+def hitmap_format(read_names, offsets, words, target_names):
+    """mic_hitmap_format: the text of exe/cuCLARK --hit-maps without its header line, as bytes.  read_names: one per read (bytes or
+    str, as the indexers cut them); offsets u32[n + 1], words u32; target_names: one per target."""
+    L = _lib.load()
+    enc = lambda s: s.encode() if isinstance(s, str) else bytes(s)
+    n, T = len(read_names), len(target_names)
+    off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+    wd = np.ascontiguousarray(words, np.uint32).reshape(-1)
+    assert off.size == n + 1 and (n == 0 or int(off[-1]) <= wd.size)
+    rn = (C.c_char_p * max(n, 1))(*[enc(s) for s in read_names])
+    tn = (C.c_char_p * max(T, 1))(*[enc(s) for s in target_names])
+    args = (rn, n, off.ctypes.data, wd.ctypes.data if wd.size else None, tn, T)
+    ln = L.mic_hitmap_format(*args, None, 0)
+    if ln < 0:
+        raise ValueError(f"mic_hitmap_format: invalid argument ({ln})")
+    buf = C.create_string_buffer(ln + 1)
+    assert L.mic_hitmap_format(*args, buf, ln + 1) == ln
+    return buf.raw[:ln]
+
+
 def rollup_check(n_targets, group_of):
     """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
     1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""

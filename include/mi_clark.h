@@ -648,6 +648,58 @@ int mic_split_device(mic_engine* e, const uint8_t* d_text, size_t nb, const uint
 int mic_split_host(const uint8_t* text, size_t nb, const uint64_t* rec_start, size_t n_reads, const uint32_t* results, const uint32_t* norm,
                    int k, uint32_t n_targets, const mic_abund_filter* filter, int which, uint8_t* out, uint64_t totals[4]);
 
+/* ---- hit maps: per read, the runs of k-mer assignments along it, made on the device (csrc/mic_hitmap.h: the rule, shared by host and device) ----
+ * Every other output is an aggregate; a hit map says WHERE along a read the hits fall.  Read r is its packed parts as the packer wrote
+ * them; part p has nk = plen - k + 1 k-mer positions, position i the 1-based label the table gives its k-mer (0: in no target, above
+ * num_targets, or not this engine's to answer).  A run is a maximal stretch of equal labels inside one part.
+ *   words    u32: per part, in order, one word (label << 16) | len per run (1 <= len <= 65535); between two consecutive parts one
+ *            separator word 0; a read without parts has none.  A sub-part cut of a run longer than MIC_MAX_PART shows as a separator
+ *            and a label run across it as two runs: the packed form cannot tell a cut from an 'N'.
+ *   offsets  u32[n_reads + 1]: exclusive prefix sums of the words per read
+ *   text     one line per read in input order, "<name>,<map>\n": <name> as the result CSV prints it (cut at a separator, at most 39
+ *            bytes), <map> the tokens joined by single spaces - a run "<target name>:<len>" ("0:<len>" for label 0), a separator "|".
+ *            exe/cuCLARK --hit-maps puts MIC_HITMAP_HEADER in front.
+ * Per read the sum of len over the words with a label equals result word 0, per target the count of the sparse row, over all words
+ * the sum of nk over the parts.  The map is never truncated: the kernel runs twice (count, exclusive sum, fill), a read whose result
+ * row has sum 0 is not probed (its map is 0:nk per part).
+ * mic_hitmap_device      the kernels alone on caller-owned device memory: packed reads as for mic_query_device, d_results the reads'
+ *                        result rows, d_offsets (n_reads + 1 u32), d_words (cap_words u32).  With d_words NULL or cap_words below the
+ *                        total only d_offsets and *n_words are filled (d_words is left untouched): size, then call again
+ *                        (mic_ingest_fetch_packed's convention).  Synchronous on `stream` (NULL = the engine's stream).
+ *                        MIC_E_UNSUPPORTED on a sharded or parted table, or when the maps need more than 2^32 - 1 words.
+ * mic_hitmap_start / _stop  engine state, next to mic_split_start: from then on every mic_ingest_classify batch of this engine that
+ *                        returns MIC_INGEST_OK gets its map and its text behind the query, on the slot's stream, with and without
+ *                        MIC_INGEST_NO_CSV, for plain, resident and paired texts (mates are parts of the merged read).  The slot's
+ *                        buffers (counts, offsets, scan storage, words, text and its pinned twin) are allocated by mic_ingest_alloc
+ *                        when the maps are started by then, else with the slot's first such batch; the word and the text buffer grow
+ *                        when a batch needs more and never shrink (first sizes: max_bytes / 64 words, max_bytes / 4 bytes of text).  Not started: nothing is allocated, nothing is launched.  While
+ *                        started, mic_ingest_classify_group with more than one engine returns MIC_E_UNSUPPORTED; so does
+ *                        mic_hitmap_start on a sharded or parted table.
+ * mic_ingest_hitmap_text the text of the slot's last batch (no header line): a pointer into a pinned buffer of the slot, valid until
+ *                        the slot's next call.  MIC_E_STATE when the last batch left none (handed back, or not started).
+ * mic_batch_hitmap       the maps of a batch of the batch API (after mic_batch_wait; its packed reads and results are still on the
+ *                        device) into host arrays: offsets (off_cap >= the batch's reads + 1, else not written), words with the
+ *                        two-call sizing of mic_hitmap_device.  Synchronous.
+ * mic_hitmap_runs_host   the rule's run-length encoding on the CPU (no device needed): labels per k-mer position, part after part
+ *                        (label 0 or above n_targets: no target), part_nk[p] positions in part p (0: the part is skipped); returns the
+ *                        number of words (written when they fit cap; words may be NULL to ask) or MIC_E_INVALID (a part of more than
+ *                        65 535 positions, a null argument).
+ * mic_hitmap_format      the text (no header line) of n_reads reads: read_names (the names as the indexers cut them, mic_index_reads'
+ *                        [name_s, name_e); printed like mic_csv_line prints them: a name of 40 bytes or more as its first 39),
+ *                        offsets, words, target names.  Returns the length (written with a terminator when it fits cap; buf may be
+ *                        NULL to ask) or MIC_E_INVALID (a null name, descending offsets).  A label above n_targets prints as the
+ *                        CSV's NA; the kernels never write one. */
+#define MIC_HITMAP_HEADER "Object_ID,Hit_map\n"
+int mic_hitmap_device(mic_engine* e, const uint32_t* d_reads_pointer, const uint16_t* d_containers, size_t n_reads, const uint32_t* d_results,
+                      uint32_t* d_offsets, uint32_t* d_words, size_t cap_words, uint64_t* n_words, void* stream);
+int mic_hitmap_start(mic_engine* e);
+int mic_hitmap_stop(mic_engine* e);
+int mic_ingest_hitmap_text(mic_engine* e, size_t slot, const uint8_t** text, uint64_t* bytes);
+int mic_batch_hitmap(mic_engine* e, size_t batch, uint32_t* offsets, size_t off_cap, uint32_t* words, size_t cap_words, uint64_t* n_words);
+long mic_hitmap_runs_host(const uint32_t* labels, const uint32_t* part_nk, size_t n_parts, uint32_t n_targets, uint32_t* words, size_t cap);
+long mic_hitmap_format(const char* const* read_names, size_t n_reads, const uint32_t* offsets, const uint32_t* words,
+                       const char* const* target_names, uint32_t n_targets, char* buf, size_t cap);
+
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */
 int mic_format_ratio_g(uint32_t num, uint32_t den, char* out16);

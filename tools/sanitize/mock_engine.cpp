@@ -224,6 +224,11 @@ int mic_rollup_stop(mic_engine*) { return MIC_OK; }
 int mic_split_start(mic_engine*, const mic_abund_filter*, int) { return MIC_OK; }
 int mic_split_stop(mic_engine*) { return MIC_OK; }
 int mic_ingest_split_text(mic_engine*, size_t, const uint8_t**, uint64_t*, uint64_t*, const uint8_t**, uint64_t*, uint64_t*) { return MIC_E_STATE; }
+// hit maps: likewise, the mock probes nothing (mic_hitmap_runs_host / _format are mic_host.cpp's and under test)
+int mic_hitmap_start(mic_engine*) { return MIC_OK; }
+int mic_hitmap_stop(mic_engine*) { return MIC_OK; }
+int mic_ingest_hitmap_text(mic_engine*, size_t, const uint8_t**, uint64_t*) { return MIC_E_STATE; }
+int mic_batch_hitmap(mic_engine*, size_t, uint32_t*, size_t, uint32_t*, size_t, uint64_t*) { return MIC_E_STATE; }
 }  // extern "C"
 
 namespace {
