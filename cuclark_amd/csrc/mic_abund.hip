@@ -10,12 +10,6 @@
 
 #include <string.h>
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicAbund* mic_engine_abund(mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
 namespace {
 
 __global__ void __launch_bounds__(256) abund_kernel(const uint32_t* __restrict__ results, const uint32_t* __restrict__ norm, uint32_t norm_sub,
@@ -51,9 +45,6 @@ hipError_t mic_launch_abund(const uint32_t* results, const uint32_t* norm, uint3
   return hipGetLastError();
 }
 
-#define ATRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int mic_abundance_start(mic_engine* e, const mic_abund_filter* filter) {
@@ -62,15 +53,15 @@ int mic_abundance_start(mic_engine* e, const mic_abund_filter* filter) {
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  ATRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   MicAbund& a = *mic_engine_abund(e);
   if (!a.d_counts || a.n_words != nt + 2) {
-    if (a.d_counts) { ATRY(hipDeviceSynchronize()); ATRY(hipFree(a.d_counts)); a.d_counts = nullptr; }
-    ATRY(hipMalloc(&a.d_counts, (size_t)(nt + 2) * 8));
+    if (a.d_counts) { MIC_TRY(hipDeviceSynchronize()); MIC_TRY(hipFree(a.d_counts)); a.d_counts = nullptr; }
+    MIC_TRY(hipMalloc(&a.d_counts, (size_t)(nt + 2) * 8));
     a.n_words = nt + 2;
   }
-  ATRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
-  ATRY(hipMemset(a.d_counts, 0, (size_t)a.n_words * 8));
+  MIC_TRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
+  MIC_TRY(hipMemset(a.d_counts, 0, (size_t)a.n_words * 8));
   a.conf_num = filter->conf_num; a.conf_den = filter->conf_den; a.gamma_num = filter->gamma_num; a.gamma_den = filter->gamma_den;
   a.on = true;
   return MIC_OK;
@@ -84,9 +75,9 @@ int mic_abundance_fetch(mic_engine* e, uint64_t* counts, size_t n) {
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  ATRY(hipSetDevice(dev));
-  ATRY(hipDeviceSynchronize());
-  ATRY(hipMemcpy(counts, a.d_counts, n * 8, hipMemcpyDeviceToHost));
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipDeviceSynchronize());
+  MIC_TRY(hipMemcpy(counts, a.d_counts, n * 8, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
@@ -105,11 +96,11 @@ int mic_abundance_device(mic_engine* e, const uint32_t* d_results, const uint32_
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  ATRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   MicAbund a;
   a.conf_num = filter->conf_num; a.conf_den = filter->conf_den; a.gamma_num = filter->gamma_num; a.gamma_den = filter->gamma_den;
   hipStream_t s = stream ? (hipStream_t)stream : mic_engine_stream(e);
-  ATRY(mic_launch_abund(d_results, d_norm, 0, n_reads, k, nt, a, (unsigned long long*)d_counts, nullptr, s));
+  MIC_TRY(mic_launch_abund(d_results, d_norm, 0, n_reads, k, nt, a, (unsigned long long*)d_counts, nullptr, s));
   return MIC_OK;
 }
 

@@ -18,12 +18,6 @@
 
 #include <stdlib.h>
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicDensity* mic_engine_density(mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
 namespace {
 
 constexpr uint32_t kReadsPerBlock = 1024;       // below this many reads per block the grid shrinks instead: every block pays a zero and a flush of the table
@@ -100,9 +94,6 @@ hipError_t mic_launch_density(const uint32_t* results, const uint32_t* norm, uin
   return hipGetLastError();
 }
 
-#define DTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int mic_density_start(mic_engine* e) {
@@ -110,11 +101,11 @@ int mic_density_start(mic_engine* e) {
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  DTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   MicDensity& d = *mic_engine_density(e);
-  if (!d.d_counts) DTRY(hipMalloc(&d.d_counts, (size_t)MIC_DENSITY_WORDS * 8));
-  DTRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
-  DTRY(hipMemset(d.d_counts, 0, (size_t)MIC_DENSITY_WORDS * 8));
+  if (!d.d_counts) MIC_TRY(hipMalloc(&d.d_counts, (size_t)MIC_DENSITY_WORDS * 8));
+  MIC_TRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
+  MIC_TRY(hipMemset(d.d_counts, 0, (size_t)MIC_DENSITY_WORDS * 8));
   d.on = true;
   return MIC_OK;
 }
@@ -127,9 +118,9 @@ int mic_density_fetch(mic_engine* e, uint64_t* counts, size_t n) {
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  DTRY(hipSetDevice(dev));
-  DTRY(hipDeviceSynchronize());
-  DTRY(hipMemcpy(counts, d.d_counts, n * 8, hipMemcpyDeviceToHost));
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipDeviceSynchronize());
+  MIC_TRY(hipMemcpy(counts, d.d_counts, n * 8, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
@@ -145,9 +136,9 @@ int mic_density_device(mic_engine* e, const uint32_t* d_results, const uint32_t*
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  DTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   hipStream_t s = stream ? (hipStream_t)stream : mic_engine_stream(e);
-  DTRY(mic_launch_density(d_results, d_norm, 0, n_reads, k, nt, ncu, (unsigned long long*)d_counts, nullptr, s));
+  MIC_TRY(mic_launch_density(d_results, d_norm, 0, n_reads, k, nt, ncu, (unsigned long long*)d_counts, nullptr, s));
   return MIC_OK;
 }
 

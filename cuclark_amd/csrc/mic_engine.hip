@@ -22,23 +22,7 @@
 #include <utility>
 #include <vector>
 
-int mic_bind_thread_near_device(int device, int on);   // below: host memory near the device
-bool mic_peer_enable(int from, int to);                 // below: several devices in one process
-void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-}  // namespace
+static thread_local char g_err[512] = "";     // mic_last_error's text: mic_set_error writes it
 thread_local uint64_t mic_build_reserved_hbm = 0;
 
 // ---- streams and events: pooled for the life of the process, never destroyed -------------------------------------------------------
@@ -120,9 +104,6 @@ std::mutex g_report_mu;
 std::string g_report;     // stage times of the last table build that FINISHED in this process, one "name: seconds" per line
 thread_local std::string t_report;   // ... of the build running on this thread
 
-#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return fail(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 struct Batch {
   uint32_t* h_rp = nullptr; uint16_t* h_cont = nullptr;
   uint32_t* d_rp = nullptr; uint16_t* d_cont = nullptr;
@@ -184,7 +165,7 @@ namespace {
 const uint32_t kFlaggedCap = 1u << 16;
 
 int set_device(const mic_engine* e) {
-  HIPTRY(hipSetDevice(e->device));
+  MIC_TRY(hipSetDevice(e->device));
   return MIC_OK;
 }
 
@@ -226,9 +207,9 @@ void fill_table(mic_engine* e, const MicBuildOut& b, uint64_t htsize, uint64_t s
 }
 
 int check_shard(uint64_t htsize, uint64_t& s0, uint64_t& s1) {
-  if (htsize < 2 || htsize > 0xFFFFFFF0ULL) return fail(MIC_E_INVALID, "unsupported table size %llu", (unsigned long long)htsize);
+  if (htsize < 2 || htsize > 0xFFFFFFF0ULL) return mic_set_error(MIC_E_INVALID, "unsupported table size %llu", (unsigned long long)htsize);
   if (s1 == 0) s1 = htsize;
-  if (s0 >= s1 || s1 > htsize) return fail(MIC_E_INVALID, "bad shard [%llu,%llu) of %llu", (unsigned long long)s0,
+  if (s0 >= s1 || s1 > htsize) return mic_set_error(MIC_E_INVALID, "bad shard [%llu,%llu) of %llu", (unsigned long long)s0,
                                            (unsigned long long)s1, (unsigned long long)htsize);
   return MIC_OK;
 }
@@ -274,12 +255,12 @@ int upload_file_range_multi(FILE* f, const std::vector<UploadDst>& dsts, const c
   const uint64_t bytes = end - off;
   int dev_now = 0;
   hipGetDevice(&dev_now);
-  if (!st->get(dsts[0].device)) rc = fail(MIC_E_NOMEM, "pinned staging alloc failed");
+  if (!st->get(dsts[0].device)) rc = mic_set_error(MIC_E_NOMEM, "pinned staging alloc failed");
   stage[0] = st->buf[0]; stage[1] = st->buf[1];
   mic_bind_thread_near_device(dsts[0].device, 1);
   for (size_t i = 0; i < 2 * nd && rc == MIC_OK; ++i) {
     if (hipSetDevice(dsts[i % nd].device) != hipSuccess || mic_event_get(&ev[i], false) != hipSuccess)
-      rc = fail(MIC_E_HIP, "event create failed");
+      rc = mic_set_error(MIC_E_HIP, "event create failed");
   }
   uint64_t done = 0; int cur = 0;
   std::vector<char> used(2 * nd, 0);
@@ -291,7 +272,7 @@ int upload_file_range_multi(FILE* f, const std::vector<UploadDst>& dsts, const c
     if (!wanted) { done += n; continue; }                // (a gap between the destinations' ranges)
     for (size_t d = 0; d < nd; ++d)
       if (used[(size_t)cur * nd + d]) {
-        if (hipEventSynchronize(ev[(size_t)cur * nd + d]) != hipSuccess) { rc = fail(MIC_E_HIP, "event sync failed"); break; }
+        if (hipEventSynchronize(ev[(size_t)cur * nd + d]) != hipSuccess) { rc = mic_set_error(MIC_E_HIP, "event sync failed"); break; }
         used[(size_t)cur * nd + d] = 0;
       }
     if (rc != MIC_OK) break;
@@ -313,14 +294,14 @@ int upload_file_range_multi(FILE* f, const std::vector<UploadDst>& dsts, const c
         });
       }
       for (auto& t : th) t.join();
-      if (short_read) { rc = fail(MIC_E_IO, "%s is shorter than the bucket sizes imply", what); break; }
+      if (short_read) { rc = mic_set_error(MIC_E_IO, "%s is shorter than the bucket sizes imply", what); break; }
     }
     for (size_t d = 0; d < nd && rc == MIC_OK; ++d) {
       const uint64_t a = dsts[d].lo > c0 ? dsts[d].lo : c0, b = dsts[d].hi < c1 ? dsts[d].hi : c1;
       if (a >= b) continue;
       if (hipSetDevice(dsts[d].device) != hipSuccess ||
           hipMemcpyAsync((char*)dsts[d].dst + (a - dsts[d].lo), (char*)stage[cur] + (a - c0), (size_t)(b - a), hipMemcpyHostToDevice, dsts[d].stream) != hipSuccess ||
-          hipEventRecord(ev[(size_t)cur * nd + d], dsts[d].stream) != hipSuccess) rc = fail(MIC_E_HIP, "H2D copy failed");
+          hipEventRecord(ev[(size_t)cur * nd + d], dsts[d].stream) != hipSuccess) rc = mic_set_error(MIC_E_HIP, "H2D copy failed");
       used[(size_t)cur * nd + d] = 1;
     }
     cur ^= 1; done += n;
@@ -418,11 +399,11 @@ void note_fallback(const char* from, const char* to, const char* why) {
 // the other layouts answer for the part's share of the on-disk buckets, the reference's split (CuClarkDB.cu:566-574)
 int apply_part(const mic_engine* e, uint64_t htsize, uint64_t& s0, uint64_t& s1) {
   if (e->n_parts <= 1) return MIC_OK;
-  if (s0 != 0 || s1 != htsize) return fail(MIC_E_INVALID, "mic_db_set_part and an explicit bucket range exclude each other");
+  if (s0 != 0 || s1 != htsize) return mic_set_error(MIC_E_INVALID, "mic_db_set_part and an explicit bucket range exclude each other");
   int layout, m, m0; bool by_default;
   decide_layout(e, layout, by_default, m, m0);
   if (layout == MIC_LAYOUT_SUPER || layout == MIC_LAYOUT_SUPER2) return MIC_OK;
-  if (htsize < e->n_parts) return fail(MIC_E_INVALID, "more parts (%u) than buckets (%llu)", e->n_parts, (unsigned long long)htsize);
+  if (htsize < e->n_parts) return mic_set_error(MIC_E_INVALID, "more parts (%u) than buckets (%llu)", e->n_parts, (unsigned long long)htsize);
   s0 = (uint64_t)((unsigned __int128)htsize * e->part / e->n_parts);
   s1 = (uint64_t)((unsigned __int128)htsize * (e->part + 1) / e->n_parts);
   return MIC_OK;
@@ -471,7 +452,7 @@ int build_from_device(mic_engine* e, const uint8_t* d_sizes_shard, uint64_t htsi
   if (layout == MIC_LAYOUT_DIRECT)
     rc = mic_build_table(d_sizes_shard, s1 - s0, d_keys_shard, key_bytes, d_labels_shard, sampling, rank_base,
                          e->slot_class, e->stream, &b, err, sizeof(err));
-  if (rc != 0) return fail(rc, "table build: %s", err);
+  if (rc != 0) return mic_set_error(rc, "table build: %s", err);
   fill_table(e, b, htsize, s0, s1, key_bytes, sampling, layout, m);
   { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
     mic_build_report_add("table build, total", (t.tv_sec - t_b0.tv_sec) + (t.tv_nsec - t_b0.tv_nsec) / 1e9); }
@@ -505,9 +486,9 @@ int run_dense(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, const
   if (!d_ids) {
     std::vector<uint32_t> iota(n_ids);
     for (size_t i = 0; i < n_ids; ++i) iota[i] = (uint32_t)i;
-    HIPTRY(hipMalloc(&d_iota, n_ids * 4));
+    MIC_TRY(hipMalloc(&d_iota, n_ids * 4));
     hipError_t he = hipMemcpy(d_iota, iota.data(), n_ids * 4, hipMemcpyHostToDevice);
-    if (he != hipSuccess) { hipFree(d_iota); return fail(MIC_E_HIP, "dense path: %s", hipGetErrorString(he)); }
+    if (he != hipSuccess) { hipFree(d_iota); return mic_set_error(MIC_E_HIP, "dense path: %s", hipGetErrorString(he)); }
     d_ids = d_iota;
   }
   // process in slabs of at most ~1 GiB of counters
@@ -516,14 +497,14 @@ int run_dense(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, const
   if (slab > n_ids) slab = n_ids;
   uint32_t* d_counts = nullptr;
   hipError_t me = hipMalloc(&d_counts, slab * (size_t)T * 4);
-  if (me != hipSuccess) { if (d_iota) hipFree(d_iota); return fail(MIC_E_NOMEM, "dense path: %s", hipGetErrorString(me)); }
+  if (me != hipSuccess) { if (d_iota) hipFree(d_iota); return mic_set_error(MIC_E_NOMEM, "dense path: %s", hipGetErrorString(me)); }
   int rc = MIC_OK;
   for (size_t off = 0; off < n_ids && rc == MIC_OK; off += slab) {
     size_t n = n_ids - off < slab ? n_ids - off : slab;
     hipError_t he = mic_launch_dense_count(e->table, e->slot_class, d_rp, d_cont, d_ids + off, n, T, d_counts, s);
     if (he == hipSuccess) he = mic_launch_dense_finish(d_counts, d_ids + off, n, T, d_results, d_rows, e->cfg.row_words, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
-    if (he != hipSuccess) rc = fail(MIC_E_HIP, "dense path: %s", hipGetErrorString(he));
+    if (he != hipSuccess) rc = mic_set_error(MIC_E_HIP, "dense path: %s", hipGetErrorString(he));
   }
   hipFree(d_counts);
   if (d_iota) hipFree(d_iota);
@@ -605,7 +586,7 @@ int mic_set_error(int code, const char* fmt, ...) {
 }
 
 int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   *t = e->table;
   if (!e->db_loaded) t->slots = nullptr;
   *slot_class = e->slot_class; *n_cu = e->n_cu; *device = e->device; *k = e->cfg.k; *n_targets = e->cfg.num_targets;
@@ -667,29 +648,29 @@ const char* mic_last_error(void) { return g_err; }
 int mic_device_count(int* count) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) { *count = 0; return fail(MIC_E_NODEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { *count = 0; return mic_set_error(MIC_E_NODEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
   *count = n;
   return MIC_OK;
 }
 
 int mic_create(const mic_config* cfg, mic_engine** out) {
-  if (!cfg || !out) return fail(MIC_E_INVALID, "null argument");
-  if (cfg->k < 2 || cfg->k > 32) return fail(MIC_E_INVALID, "The k-mer length should be in [2,32].");
-  if (cfg->num_targets > 65535) return fail(MIC_E_INVALID, "too many targets (%u > 65535)", cfg->num_targets);
-  if (cfg->layout > MIC_LAYOUT_SUPER2) return fail(MIC_E_INVALID, "unknown table layout %u", cfg->layout);
+  if (!cfg || !out) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (cfg->k < 2 || cfg->k > 32) return mic_set_error(MIC_E_INVALID, "The k-mer length should be in [2,32].");
+  if (cfg->num_targets > 65535) return mic_set_error(MIC_E_INVALID, "too many targets (%u > 65535)", cfg->num_targets);
+  if (cfg->layout > MIC_LAYOUT_SUPER2) return mic_set_error(MIC_E_INVALID, "unknown table layout %u", cfg->layout);
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    return fail(MIC_E_NODEVICE, "no HIP device available: the MI355X engine cannot run (there is no CPU fallback)");
+    return mic_set_error(MIC_E_NODEVICE, "no HIP device available: the MI355X engine cannot run (there is no CPU fallback)");
   int dev = cfg->device;
   if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-  if (dev >= n) return fail(MIC_E_INVALID, "device %d out of range (%d devices)", dev, n);
+  if (dev >= n) return mic_set_error(MIC_E_INVALID, "device %d out of range (%d devices)", dev, n);
   hipDeviceProp_t prop;
-  HIPTRY(hipSetDevice(dev));
-  HIPTRY(hipGetDeviceProperties(&prop, dev));
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipGetDeviceProperties(&prop, dev));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(MIC_E_NODEVICE, "device %d is %s; this library carries gfx950 (MI355X) code objects only", dev, prop.gcnArchName);
+    return mic_set_error(MIC_E_NODEVICE, "device %d is %s; this library carries gfx950 (MI355X) code objects only", dev, prop.gcnArchName);
   mic_engine* e = new (std::nothrow) mic_engine();
-  if (!e) return fail(MIC_E_NOMEM, "out of host memory");
+  if (!e) return mic_set_error(MIC_E_NOMEM, "out of host memory");
   e->cfg = *cfg;
   if (e->cfg.num_batches == 0) e->cfg.num_batches = 1;
   if (e->cfg.row_words == 0) e->cfg.row_words = 16;
@@ -704,7 +685,7 @@ int mic_create(const mic_config* cfg, mic_engine** out) {
   if (he == hipSuccess) he = mic_event_get(&e->ev0, true);
   if (he == hipSuccess) he = mic_event_get(&e->ev1, true);
   if (he == hipSuccess) he = hipMalloc(&e->d_flagged, (size_t)(kFlaggedCap + 1) * 4);
-  if (he != hipSuccess) { mic_destroy(e); return fail(MIC_E_HIP, "engine setup: %s", hipGetErrorString(he)); }
+  if (he != hipSuccess) { mic_destroy(e); return mic_set_error(MIC_E_HIP, "engine setup: %s", hipGetErrorString(he)); }
   e->flagged_cap = kFlaggedCap;
   *out = e;
   return MIC_OK;
@@ -737,7 +718,7 @@ int mic_destroy(mic_engine* e) {
 }
 
 int mic_db_unload(mic_engine* e) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   int rc = set_device(e);
   if (rc) return rc;
   hipDeviceSynchronize();
@@ -750,8 +731,8 @@ int mic_db_unload(mic_engine* e) {
 }
 
 int mic_db_get_info(const mic_engine* e, mic_db_info* info) {
-  if (!e || !info) return fail(MIC_E_INVALID, "null argument");
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
+  if (!e || !info) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
   *info = e->info;
   return MIC_OK;
 }
@@ -764,24 +745,24 @@ const char* mic_db_last_build_report(void) {
 }
 
 int mic_db_reserve_hbm(mic_engine* e, uint64_t bytes) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   e->reserve_hbm = bytes;
   return MIC_OK;
 }
 
 int mic_db_set_part(mic_engine* e, uint32_t part, uint32_t n_parts) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
-  if (n_parts > 1 && part >= n_parts) return fail(MIC_E_INVALID, "part %u of %u", part, n_parts);
-  if (n_parts > 65536) return fail(MIC_E_INVALID, "too many parts");
-  if (e->db_loaded) return fail(MIC_E_STATE, "set the part before the database is loaded");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  if (n_parts > 1 && part >= n_parts) return mic_set_error(MIC_E_INVALID, "part %u of %u", part, n_parts);
+  if (n_parts > 65536) return mic_set_error(MIC_E_INVALID, "too many parts");
+  if (e->db_loaded) return mic_set_error(MIC_E_STATE, "set the part before the database is loaded");
   e->part = n_parts > 1 ? part : 0; e->n_parts = n_parts > 1 ? n_parts : 0;
   return MIC_OK;
 }
 
 int mic_db_load_device(mic_engine* e, const uint8_t* d_sizes, uint64_t htsize, const void* d_keys, int key_bytes,
                        const uint16_t* d_labels, uint32_t sampling, uint64_t s0, uint64_t s1) {
-  if (!e || !d_sizes || !d_keys || !d_labels) return fail(MIC_E_INVALID, "null argument");
-  if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) return fail(MIC_E_INVALID, "key_bytes must be 2, 4 or 8");
+  if (!e || !d_sizes || !d_keys || !d_labels) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) return mic_set_error(MIC_E_INVALID, "key_bytes must be 2, 4 or 8");
   int rc = set_device(e);
   if (rc) return rc;
   if ((rc = check_shard(htsize, s0, s1))) return rc;
@@ -789,15 +770,15 @@ int mic_db_load_device(mic_engine* e, const uint8_t* d_sizes, uint64_t htsize, c
   if (e->db_loaded) mic_db_unload(e);
   uint64_t base_elems = 0, base_rank = 0;
   if (s0 > 0 && mic_reduce_sizes(d_sizes, s0, &base_elems, &base_rank, e->stream) != 0)
-    return fail(MIC_E_HIP, "size reduction failed");
+    return mic_set_error(MIC_E_HIP, "size reduction failed");
   return build_from_device(e, d_sizes + s0, htsize, s0, s1, (const char*)d_keys + base_elems * key_bytes, key_bytes,
                            d_labels + base_elems, sampling, base_rank);
 }
 
 int mic_db_load_host(mic_engine* e, const uint8_t* sizes, uint64_t htsize, const void* keys, int key_bytes,
                      const uint16_t* labels, uint32_t sampling, uint64_t s0, uint64_t s1) {
-  if (!e || !sizes || !keys || !labels) return fail(MIC_E_INVALID, "null argument");
-  if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) return fail(MIC_E_INVALID, "key_bytes must be 2, 4 or 8");
+  if (!e || !sizes || !keys || !labels) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) return mic_set_error(MIC_E_INVALID, "key_bytes must be 2, 4 or 8");
   int rc = set_device(e);
   if (rc) return rc;
   if ((rc = check_shard(htsize, s0, s1))) return rc;
@@ -813,7 +794,7 @@ int mic_db_load_host(mic_engine* e, const uint8_t* sizes, uint64_t htsize, const
   if (he == hipSuccess) he = hipMemcpy(d_sz, sizes + s0, s1 - s0, hipMemcpyHostToDevice);
   if (he == hipSuccess && n_el) he = hipMemcpy(d_ky, (const char*)keys + base_elems * key_bytes, n_el * key_bytes, hipMemcpyHostToDevice);
   if (he == hipSuccess && n_el) he = hipMemcpy(d_lb, labels + base_elems, n_el * 2, hipMemcpyHostToDevice);
-  if (he != hipSuccess) rc = fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "upload of DB images: %s", hipGetErrorString(he));
+  if (he != hipSuccess) rc = mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "upload of DB images: %s", hipGetErrorString(he));
   else rc = build_from_device(e, d_sz, htsize, s0, s1, d_ky, key_bytes, d_lb, sampling, base_rank);
   if (d_sz) hipFree(d_sz);
   if (d_ky) hipFree(d_ky);
@@ -822,7 +803,7 @@ int mic_db_load_host(mic_engine* e, const uint8_t* sizes, uint64_t htsize, const
 }
 
 int mic_db_load_files(mic_engine* e, const char* prefix, int key_bytes, uint32_t sampling, uint64_t s0, uint64_t s1) {
-  if (!e || !prefix) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !prefix) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
   std::string p(prefix);
@@ -841,16 +822,16 @@ int mic_db_load_files(mic_engine* e, const char* prefix, int key_bytes, uint32_t
   };
   do {
     // reference: "Failed to open <file>" and read() returns false (CuClarkDB.cu:490-495)
-    if (!fs) { rc = fail(MIC_E_IO, "Failed to open %s.sz", prefix); break; }
-    if (!fk) { rc = fail(MIC_E_IO, "Failed to open %s.ky", prefix); break; }
-    if (!fl) { rc = fail(MIC_E_IO, "Failed to open %s.lb", prefix); break; }
+    if (!fs) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.sz", prefix); break; }
+    if (!fk) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.ky", prefix); break; }
+    if (!fl) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.lb", prefix); break; }
     fseeko(fs, 0, SEEK_END);
     uint64_t htsize = (uint64_t)ftello(fs);
     fseeko(fs, 0, SEEK_SET);
     if ((rc = check_shard(htsize, s0, s1))) break;
     if ((rc = apply_part(e, htsize, s0, s1))) break;
     if (key_bytes == 0) key_bytes = mic_key_bytes_rule(htsize, e->cfg.k);
-    if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) { rc = fail(MIC_E_INVALID, "key_bytes must be 2, 4 or 8"); break; }
+    if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) { rc = mic_set_error(MIC_E_INVALID, "key_bytes must be 2, 4 or 8"); break; }
     uint64_t base_elems = 0, base_rank = 0, n_el = 0, nz = 0;
     if (e->db_loaded) mic_db_unload(e);
     if (s0 == 0) {
@@ -858,17 +839,17 @@ int mic_db_load_files(mic_engine* e, const char* prefix, int key_bytes, uint32_t
       // buffers (several readers, as for .ky and .lb) and are summed THERE - reading the 1.6 GB into pageable host memory and
       // summing them with one thread each were 0.68 s of the command line's start (0.44 s with eight threads each)
       hipError_t he = hipMalloc(&d_sz, s1);
-      if (he != hipSuccess) { rc = fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
+      if (he != hipSuccess) { rc = mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
       if ((rc = upload_file_range(fs, 0, s1, d_sz, e->stream, "the .sz file", &stage))) break;
-      if (mic_reduce_sizes(d_sz, s1, &n_el, &nz, e->stream) != 0) { rc = fail(MIC_E_HIP, "size reduction failed"); break; }
+      if (mic_reduce_sizes(d_sz, s1, &n_el, &nz, e->stream) != 0) { rc = mic_set_error(MIC_E_HIP, "size reduction failed"); break; }
       lap("read + upload .sz, bucket sizes summed on the device");
       he = hipMalloc(&d_ky, n_el * key_bytes + 16);
       if (he == hipSuccess) he = hipMalloc(&d_lb, n_el * 2 + 16);
-      if (he != hipSuccess) { rc = fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
+      if (he != hipSuccess) { rc = mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
     } else {
       h_sz = (uint8_t*)malloc(htsize);
-      if (!h_sz) { rc = fail(MIC_E_NOMEM, "out of host memory for bucket sizes"); break; }
-      if (!read_file_parallel(fs, h_sz, htsize)) { rc = fail(MIC_E_IO, "short read on %s.sz", prefix); break; }
+      if (!h_sz) { rc = mic_set_error(MIC_E_NOMEM, "out of host memory for bucket sizes"); break; }
+      if (!read_file_parallel(fs, h_sz, htsize)) { rc = mic_set_error(MIC_E_IO, "short read on %s.sz", prefix); break; }
       lap("read .sz");
       sum_sizes_parallel(h_sz, 0, s0, &base_elems, &base_rank);
       sum_sizes_parallel(h_sz, s0, s1, &n_el, &nz);
@@ -877,7 +858,7 @@ int mic_db_load_files(mic_engine* e, const char* prefix, int key_bytes, uint32_t
       if (he == hipSuccess) he = hipMalloc(&d_ky, n_el * key_bytes + 16);
       if (he == hipSuccess) he = hipMalloc(&d_lb, n_el * 2 + 16);
       if (he == hipSuccess) he = hipMemcpy(d_sz, h_sz + s0, s1 - s0, hipMemcpyHostToDevice);
-      if (he != hipSuccess) { rc = fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
+      if (he != hipSuccess) { rc = mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation: %s", hipGetErrorString(he)); break; }
     }
     lap("allocate + upload .sz");
     if ((rc = upload_file_range(fk, base_elems * key_bytes, n_el * key_bytes, d_ky, e->stream, "the .ky file", &stage))) break;
@@ -901,7 +882,7 @@ int mic_db_load_files(mic_engine* e, const char* prefix, int key_bytes, uint32_t
 int mic_batches_alloc(mic_engine* e, size_t num_reads_total, size_t max_reads, size_t max_containers,
                       const uint32_t* index_batches, int extended, uint32_t** results, uint32_t** rows,
                       uint32_t** reads_pointer, uint16_t** containers) {
-  if (!e || !index_batches || !results || !reads_pointer || !containers) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !index_batches || !results || !reads_pointer || !containers) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
   free_batches(e);
@@ -921,9 +902,9 @@ int mic_batches_alloc(mic_engine* e, size_t num_reads_total, size_t max_reads, s
     hipError_t he = hipHostMalloc(&e->h_block, h_total, hipHostMallocDefault);
     if (he == hipSuccess) memset(e->h_block, 0, h_total);
     mic_bind_thread_near_device(e->device, 0);
-    HIPTRY(he);
+    MIC_TRY(he);
   }
-  HIPTRY(hipMalloc(&e->d_block, d_total));
+  MIC_TRY(hipMalloc(&e->d_block, d_total));
   char* hp = (char*)e->h_block; char* dp = (char*)e->d_block;
   e->h_results = (uint32_t*)hp; hp += h_res;
   if (extended) { e->h_rows = (uint32_t*)hp; hp += h_rows; }
@@ -942,10 +923,10 @@ int mic_batches_alloc(mic_engine* e, size_t num_reads_total, size_t max_reads, s
     if (extended) { B.d_rows = (uint32_t*)dp; dp += sz_rows; }
     B.d_flagged = (uint32_t*)dp; dp += sz_fl;
     B.d_crowd = (uint32_t*)dp; dp += sz_crowd;
-    HIPTRY(mic_stream_get(&B.stream));
-    HIPTRY(mic_event_get(&B.done, false));
-    HIPTRY(mic_event_get(&B.ev_up, false));
-    HIPTRY(mic_event_get(&B.ev_k, false));
+    MIC_TRY(mic_stream_get(&B.stream));
+    MIC_TRY(mic_event_get(&B.done, false));
+    MIC_TRY(mic_event_get(&B.ev_up, false));
+    MIC_TRY(mic_event_get(&B.ev_k, false));
     reads_pointer[b] = B.h_rp;
     containers[b] = B.h_cont;
   }
@@ -955,10 +936,10 @@ int mic_batches_alloc(mic_engine* e, size_t num_reads_total, size_t max_reads, s
 }
 
 int mic_batch_ready(mic_engine* e, size_t batch, size_t n_reads, size_t n_containers) {
-  if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad batch id");
   Batch& B = e->batches[batch];
   if (n_reads > B.max_reads || n_containers > B.max_cont)
-    return fail(MIC_E_INVALID, "batch %zu exceeds its allocation (%zu reads, %zu containers)", batch, n_reads, n_containers);
+    return mic_set_error(MIC_E_INVALID, "batch %zu exceeds its allocation (%zu reads, %zu containers)", batch, n_reads, n_containers);
   B.n_reads = n_reads; B.n_cont = n_containers;
   return MIC_OK;
 }
@@ -967,57 +948,57 @@ int mic_batch_ready(mic_engine* e, size_t batch, size_t n_reads, size_t n_contai
 // otherwise they are ALREADY on device src_device in another engine's batch buffers (uploaded there, `src->ev_up` says when) and come
 // over by peer copy on this batch's stream - one upload serves every engine of a table-sharded group.
 static int batch_query_impl(mic_engine* e, size_t batch, int extended, const Batch* src, int src_device) {
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
   std::lock_guard<std::mutex> lock(e->submit_mu);
   int rc = set_device(e);
   if (rc) return rc;
   Batch& B = e->batches[batch];
-  if (extended && !B.d_rows) return fail(MIC_E_STATE, "batches were not allocated for extended results");
+  if (extended && !B.d_rows) return mic_set_error(MIC_E_STATE, "batches were not allocated for extended results");
   hipStream_t s = B.stream, up = e->up_stream, down = e->down_stream;
   if (!src) {
-    HIPTRY(hipMemcpyAsync(B.d_rp, B.h_rp, (B.n_reads + 1) * 4, hipMemcpyHostToDevice, up));
-    HIPTRY(hipMemcpyAsync(B.d_cont, B.h_cont, (B.n_cont + 16) * 2, hipMemcpyHostToDevice, up));
-    HIPTRY(hipEventRecord(B.ev_up, up));
-    HIPTRY(hipStreamWaitEvent(s, B.ev_up, 0));
+    MIC_TRY(hipMemcpyAsync(B.d_rp, B.h_rp, (B.n_reads + 1) * 4, hipMemcpyHostToDevice, up));
+    MIC_TRY(hipMemcpyAsync(B.d_cont, B.h_cont, (B.n_cont + 16) * 2, hipMemcpyHostToDevice, up));
+    MIC_TRY(hipEventRecord(B.ev_up, up));
+    MIC_TRY(hipStreamWaitEvent(s, B.ev_up, 0));
   } else {
-    HIPTRY(hipStreamWaitEvent(s, src->ev_up, 0));
-    HIPTRY(hipMemcpyPeerAsync(B.d_rp, e->device, src->d_rp, src_device, (B.n_reads + 1) * 4, s));
-    HIPTRY(hipMemcpyPeerAsync(B.d_cont, e->device, src->d_cont, src_device, (B.n_cont + 16) * 2, s));
+    MIC_TRY(hipStreamWaitEvent(s, src->ev_up, 0));
+    MIC_TRY(hipMemcpyPeerAsync(B.d_rp, e->device, src->d_rp, src_device, (B.n_reads + 1) * 4, s));
+    MIC_TRY(hipMemcpyPeerAsync(B.d_cont, e->device, src->d_cont, src_device, (B.n_cont + 16) * 2, s));
   }
-  HIPTRY(hipMemsetAsync(B.d_flagged, 0, 4, s));
+  MIC_TRY(hipMemsetAsync(B.d_flagged, 0, 4, s));
   MicQueryArgs a;
   a.t = e->table; a.reads_ptr = B.d_rp; a.cont = B.d_cont; a.n_reads = (uint32_t)B.n_reads;
   a.row_words = e->cfg.row_words; a.results = B.d_results; a.rows = extended ? B.d_rows : nullptr;
   a.flagged = B.d_flagged; a.flagged_cap = kFlaggedCap;
   mic_crowd_attach(a, B.d_crowd, B.max_reads);
-  HIPTRY(mic_launch_query(a, e->slot_class, e->n_cu, s));
-  HIPTRY(hipEventRecord(B.ev_k, s));
-  HIPTRY(hipStreamWaitEvent(down, B.ev_k, 0));
-  HIPTRY(hipMemcpyAsync(e->h_results + B.first_read * MIC_RESULT_WORDS, B.d_results, B.n_reads * MIC_RESULT_WORDS * 4,
+  MIC_TRY(mic_launch_query(a, e->slot_class, e->n_cu, s));
+  MIC_TRY(hipEventRecord(B.ev_k, s));
+  MIC_TRY(hipStreamWaitEvent(down, B.ev_k, 0));
+  MIC_TRY(hipMemcpyAsync(e->h_results + B.first_read * MIC_RESULT_WORDS, B.d_results, B.n_reads * MIC_RESULT_WORDS * 4,
                         hipMemcpyDeviceToHost, down));
   if (extended)
-    HIPTRY(hipMemcpyAsync(e->h_rows + B.first_read * (size_t)e->cfg.row_words, B.d_rows,
+    MIC_TRY(hipMemcpyAsync(e->h_rows + B.first_read * (size_t)e->cfg.row_words, B.d_rows,
                           B.n_reads * (size_t)e->cfg.row_words * 4, hipMemcpyDeviceToHost, down));
-  HIPTRY(hipMemcpyAsync(B.h_flagged, B.d_flagged, 4, hipMemcpyDeviceToHost, down));   // count only; ids stay on the device
-  HIPTRY(hipEventRecord(B.done, down));
+  MIC_TRY(hipMemcpyAsync(B.h_flagged, B.d_flagged, 4, hipMemcpyDeviceToHost, down));   // count only; ids stay on the device
+  MIC_TRY(hipEventRecord(B.done, down));
   B.scheduled = true; B.resolved = false; B.extended = extended != 0;
   return MIC_OK;
 }
 
 int mic_batch_query(mic_engine* e, size_t batch, int extended, int followup) {
   (void)followup;
-  if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad batch id");
   return batch_query_impl(e, batch, extended, nullptr, 0);
 }
 
 int mic_batch_query_group(mic_engine* const* engines, size_t n_engines, size_t batch, int extended) {
-  if (!engines || n_engines == 0 || !engines[0] || batch >= engines[0]->batches.size()) return fail(MIC_E_INVALID, "bad argument");
+  if (!engines || n_engines == 0 || !engines[0] || batch >= engines[0]->batches.size()) return mic_set_error(MIC_E_INVALID, "bad argument");
   const Batch& B0 = engines[0]->batches[batch];
   for (size_t i = 1; i < n_engines; ++i) {
     mic_engine* e = engines[i];
-    if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad engine or batch id");
+    if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad engine or batch id");
     Batch& B = e->batches[batch];
-    if (B0.n_reads > B.max_reads || B0.n_cont > B.max_cont) return fail(MIC_E_INVALID, "engine %zu: batch %zu is smaller than engine 0's", i, batch);
+    if (B0.n_reads > B.max_reads || B0.n_cont > B.max_cont) return mic_set_error(MIC_E_INVALID, "engine %zu: batch %zu is smaller than engine 0's", i, batch);
     B.n_reads = B0.n_reads; B.n_cont = B0.n_cont;
   }
   mic_peer_enable_engines(engines, n_engines);
@@ -1027,12 +1008,12 @@ int mic_batch_query_group(mic_engine* const* engines, size_t n_engines, size_t b
 }
 
 int mic_batch_wait(mic_engine* e, size_t batch) {
-  if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad batch id");
   Batch& B = e->batches[batch];
-  if (!B.scheduled) return fail(MIC_E_STATE, "batch %zu was not queried", batch);
+  if (!B.scheduled) return mic_set_error(MIC_E_STATE, "batch %zu was not queried", batch);
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(hipEventSynchronize(B.done));
+  MIC_TRY(hipEventSynchronize(B.done));
   if (!B.resolved) {
     std::lock_guard<std::mutex> lock(e->submit_mu);
     if (!B.resolved) {
@@ -1045,10 +1026,10 @@ int mic_batch_wait(mic_engine* e, size_t batch) {
           rc = run_dense(e, B.d_rp, B.d_cont, B.d_flagged + 1, nf, B.d_results, B.extended ? B.d_rows : nullptr, B.stream);
         }
         if (rc) return rc;
-        HIPTRY(hipMemcpy(e->h_results + B.first_read * MIC_RESULT_WORDS, B.d_results, B.n_reads * MIC_RESULT_WORDS * 4,
+        MIC_TRY(hipMemcpy(e->h_results + B.first_read * MIC_RESULT_WORDS, B.d_results, B.n_reads * MIC_RESULT_WORDS * 4,
                          hipMemcpyDeviceToHost));
         if (B.extended)
-          HIPTRY(hipMemcpy(e->h_rows + B.first_read * (size_t)e->cfg.row_words, B.d_rows,
+          MIC_TRY(hipMemcpy(e->h_rows + B.first_read * (size_t)e->cfg.row_words, B.d_rows,
                            B.n_reads * (size_t)e->cfg.row_words * 4, hipMemcpyDeviceToHost));
       }
       B.resolved = true;
@@ -1059,36 +1040,36 @@ int mic_batch_wait(mic_engine* e, size_t batch) {
 
 // the batch's reads into the engine's k-mer sketches (mic_ksketch_start): the same kernel the ingest path runs behind its query
 int mic_batch_ksketch(mic_engine* e, size_t batch) {
-  if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad batch id");
   Batch& B = e->batches[batch];
-  if (!B.scheduled) return fail(MIC_E_STATE, "batch %zu was not queried", batch);
+  if (!B.scheduled) return mic_set_error(MIC_E_STATE, "batch %zu was not queried", batch);
   const MicKsketch& ks = e->ksketch;
-  if (!ks.on || !ks.d_regs) return fail(MIC_E_STATE, "k-mer sketches were not started on this engine");
+  if (!ks.on || !ks.d_regs) return mic_set_error(MIC_E_STATE, "k-mer sketches were not started on this engine");
   int rc = set_device(e);
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(e->submit_mu);
-  HIPTRY(hipEventSynchronize(B.done));
-  HIPTRY(mic_launch_ksketch(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, B.n_reads, B.d_results, ks.n_targets, ks.d_regs, ks.d_hits,
+  MIC_TRY(hipEventSynchronize(B.done));
+  MIC_TRY(mic_launch_ksketch(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, B.n_reads, B.d_results, ks.n_targets, ks.d_regs, ks.d_hits,
                             nullptr, B.stream));
-  HIPTRY(hipStreamSynchronize(B.stream));
+  MIC_TRY(hipStreamSynchronize(B.stream));
   return MIC_OK;
 }
 
 // the hit maps of the batch's reads (mic_hitmap.h) into host arrays: the kernels of mic_hitmap_device on the batch's device-resident
 // packed reads and results; a first run sizes, a second fills when the caller's words hold the total
 int mic_batch_hitmap(mic_engine* e, size_t batch, uint32_t* offsets, size_t off_cap, uint32_t* words, size_t cap_words, uint64_t* n_words) {
-  if (!e || batch >= e->batches.size() || !n_words) return fail(MIC_E_INVALID, "bad argument");
+  if (!e || batch >= e->batches.size() || !n_words) return mic_set_error(MIC_E_INVALID, "bad argument");
   Batch& B = e->batches[batch];
-  if (!B.scheduled) return fail(MIC_E_STATE, "batch %zu was not queried", batch);
-  if (e->table.sharded || e->table.parted) return fail(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
+  if (!B.scheduled) return mic_set_error(MIC_E_STATE, "batch %zu was not queried", batch);
+  if (e->table.sharded || e->table.parted) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
   int rc = set_device(e);
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(e->submit_mu);
-  HIPTRY(hipEventSynchronize(B.done));
+  MIC_TRY(hipEventSynchronize(B.done));
   const size_t n = B.n_reads;
   uint32_t* d_off = nullptr; uint32_t* d_words = nullptr;
   *n_words = 0;
-  HIPTRY(hipMalloc(&d_off, (n + 1) * 4));
+  MIC_TRY(hipMalloc(&d_off, (n + 1) * 4));
   uint64_t total = 0;
   rc = mic_hitmap_run(e->table, e->slot_class, e->n_cu, B.d_rp, B.d_cont, n, B.d_results, e->cfg.num_targets, d_off, nullptr, 0, &total, B.stream);
   hipError_t he = hipSuccess;
@@ -1101,23 +1082,23 @@ int mic_batch_hitmap(mic_engine* e, size_t batch, uint32_t* offsets, size_t off_
   hipFree(d_off);
   if (d_words) hipFree(d_words);
   if (rc) return rc;
-  if (he != hipSuccess) return fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "hit maps of a batch: %s", hipGetErrorString(he));
+  if (he != hipSuccess) return mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "hit maps of a batch: %s", hipGetErrorString(he));
   *n_words = total;
   return MIC_OK;
 }
 
 int mic_batch_dense_counts(mic_engine* e, size_t batch, size_t read_in_batch, uint32_t* counts) {
-  if (!e || batch >= e->batches.size() || !counts) return fail(MIC_E_INVALID, "bad argument");
+  if (!e || batch >= e->batches.size() || !counts) return mic_set_error(MIC_E_INVALID, "bad argument");
   Batch& B = e->batches[batch];
-  if (!B.scheduled || read_in_batch >= B.n_reads) return fail(MIC_E_INVALID, "bad read index");
+  if (!B.scheduled || read_in_batch >= B.n_reads) return mic_set_error(MIC_E_INVALID, "bad read index");
   int rc = set_device(e);
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(e->submit_mu);
   const uint32_t T = e->cfg.num_targets ? e->cfg.num_targets : 1;
   uint32_t* d_counts = nullptr; uint32_t* d_id = nullptr;
   uint32_t id = (uint32_t)read_in_batch;
-  HIPTRY(hipEventSynchronize(B.done));
-  HIPTRY(hipMalloc(&d_counts, (size_t)T * 4));
+  MIC_TRY(hipEventSynchronize(B.done));
+  MIC_TRY(hipMalloc(&d_counts, (size_t)T * 4));
   hipError_t he = hipMalloc(&d_id, 4);
   if (he == hipSuccess) he = hipMemcpyAsync(d_id, &id, 4, hipMemcpyHostToDevice, B.stream);
   if (he == hipSuccess) he = mic_launch_dense_count(e->table, e->slot_class, B.d_rp, B.d_cont, d_id, 1, T, d_counts, B.stream);
@@ -1125,7 +1106,7 @@ int mic_batch_dense_counts(mic_engine* e, size_t batch, size_t read_in_batch, ui
   if (he == hipSuccess) he = hipStreamSynchronize(B.stream);
   hipFree(d_counts);
   if (d_id) hipFree(d_id);
-  if (he != hipSuccess) return fail(MIC_E_HIP, "dense counts: %s", hipGetErrorString(he));
+  if (he != hipSuccess) return mic_set_error(MIC_E_HIP, "dense counts: %s", hipGetErrorString(he));
   return MIC_OK;
 }
 
@@ -1135,18 +1116,18 @@ int mic_batch_dense_counts(mic_engine* e, size_t batch, size_t read_in_batch, ui
 // (peer copies, all engines at once on their own streams), sums and finishes them, and writes results and rows of its range
 // straight into engines[0]'s host arrays.
 int mic_batch_merge_shards(mic_engine* const* engines, size_t n_engines, size_t batch) {
-  if (!engines || n_engines == 0 || !engines[0]) return fail(MIC_E_INVALID, "bad argument");
+  if (!engines || n_engines == 0 || !engines[0]) return mic_set_error(MIC_E_INVALID, "bad argument");
   mic_engine* dst = engines[0];
-  if (batch >= dst->batches.size()) return fail(MIC_E_INVALID, "bad batch id");
+  if (batch >= dst->batches.size()) return mic_set_error(MIC_E_INVALID, "bad batch id");
   Batch& D = dst->batches[batch];
-  if (!D.d_rows || !dst->h_rows) return fail(MIC_E_STATE, "batches must be allocated and queried with extended = 1");
+  if (!D.d_rows || !dst->h_rows) return mic_set_error(MIC_E_STATE, "batches must be allocated and queried with extended = 1");
   const uint32_t rw = dst->cfg.row_words;
   for (size_t i = 0; i < n_engines; ++i) {
     mic_engine* e = engines[i];
-    if (!e || batch >= e->batches.size()) return fail(MIC_E_INVALID, "bad engine or batch id");
+    if (!e || batch >= e->batches.size()) return mic_set_error(MIC_E_INVALID, "bad engine or batch id");
     const Batch& B = e->batches[batch];
     if (!B.d_rows || e->cfg.row_words != rw || B.n_reads != D.n_reads || !B.extended)
-      return fail(MIC_E_STATE, "engine %zu: batch %zu does not match (rows, row width or read count)", i, batch);
+      return mic_set_error(MIC_E_STATE, "engine %zu: batch %zu does not match (rows, row width or read count)", i, batch);
     int rc = mic_batch_wait(e, batch);          // kernels done, flagged reads resolved inside their shard
     if (rc) return rc;
   }
@@ -1161,8 +1142,8 @@ int mic_batch_merge_shards(mic_engine* const* engines, size_t n_engines, size_t 
     if ((rc = set_device(e))) break;
     std::lock_guard<std::mutex> lock(e->submit_mu);
     if (n_engines > 1 && !J.d_peer) {
-      HIPTRY(hipMalloc(&J.d_peer, (J.max_reads + 1) * (size_t)rw * 4));
-      HIPTRY(hipMalloc(&J.d_acc, (J.max_reads + 1) * (size_t)rw * 4));
+      MIC_TRY(hipMalloc(&J.d_peer, (J.max_reads + 1) * (size_t)rw * 4));
+      MIC_TRY(hipMalloc(&J.d_acc, (J.max_reads + 1) * (size_t)rw * 4));
     }
     uint32_t* buf[2] = {J.d_rows + lo * rw, J.d_acc};   // the running sum ping-pongs between the range of the batch's own rows and a spare
     int c = 0; size_t got = 0;
@@ -1170,49 +1151,49 @@ int mic_batch_merge_shards(mic_engine* const* engines, size_t n_engines, size_t 
       if (p == j) continue;
       const Batch& P = engines[p]->batches[batch];
       uint32_t* in = J.d_peer + got * len * rw;
-      HIPTRY(hipMemcpyPeerAsync(in, e->device, P.d_rows + lo * rw, engines[p]->device, len * (size_t)rw * 4, J.stream));
-      HIPTRY(mic_launch_merge_rows(buf[c], in, buf[c ^ 1], rw, len, nullptr, J.stream));
+      MIC_TRY(hipMemcpyPeerAsync(in, e->device, P.d_rows + lo * rw, engines[p]->device, len * (size_t)rw * 4, J.stream));
+      MIC_TRY(mic_launch_merge_rows(buf[c], in, buf[c ^ 1], rw, len, nullptr, J.stream));
       c ^= 1; ++got;
     }
     uint32_t* cur = buf[c];
-    HIPTRY(mic_launch_result_from_rows(cur, rw, J.d_results + lo * MIC_RESULT_WORDS, len, J.stream));
-    HIPTRY(hipMemcpyAsync(dst->h_results + (D.first_read + lo) * MIC_RESULT_WORDS, J.d_results + lo * MIC_RESULT_WORDS,
+    MIC_TRY(mic_launch_result_from_rows(cur, rw, J.d_results + lo * MIC_RESULT_WORDS, len, J.stream));
+    MIC_TRY(hipMemcpyAsync(dst->h_results + (D.first_read + lo) * MIC_RESULT_WORDS, J.d_results + lo * MIC_RESULT_WORDS,
                           len * MIC_RESULT_WORDS * 4, hipMemcpyDeviceToHost, J.stream));
-    HIPTRY(hipMemcpyAsync(dst->h_rows + (D.first_read + lo) * (size_t)rw, cur, len * (size_t)rw * 4, hipMemcpyDeviceToHost, J.stream));
+    MIC_TRY(hipMemcpyAsync(dst->h_rows + (D.first_read + lo) * (size_t)rw, cur, len * (size_t)rw * 4, hipMemcpyDeviceToHost, J.stream));
   }
   for (size_t j = 0; j < n_engines; ++j) {
     if (set_device(engines[j]) != MIC_OK) continue;
     hipError_t he = hipStreamSynchronize(engines[j]->batches[batch].stream);
-    if (he != hipSuccess && rc == MIC_OK) rc = fail(MIC_E_HIP, "merge of the table shards: %s", hipGetErrorString(he));
+    if (he != hipSuccess && rc == MIC_OK) rc = mic_set_error(MIC_E_HIP, "merge of the table shards: %s", hipGetErrorString(he));
   }
   return rc;
 }
 
 int mic_peer_matrix(int* matrix, int n_devices) {
-  if (!matrix || n_devices < 1 || n_devices > 64) return fail(MIC_E_INVALID, "bad argument");
+  if (!matrix || n_devices < 1 || n_devices > 64) return mic_set_error(MIC_E_INVALID, "bad argument");
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n_devices > n) return fail(MIC_E_INVALID, "%d devices asked for, %d present", n_devices, n);
+  if (hipGetDeviceCount(&n) != hipSuccess || n_devices > n) return mic_set_error(MIC_E_INVALID, "%d devices asked for, %d present", n_devices, n);
   for (int i = 0; i < n_devices; ++i)
     for (int j = 0; j < n_devices; ++j) matrix[i * n_devices + j] = mic_peer_enable(i, j) ? 1 : 0;
   return MIC_OK;
 }
 
 int mic_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
-  if (!free_bytes || !total_bytes) return fail(MIC_E_INVALID, "null argument");
+  if (!free_bytes || !total_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
   int cur = 0;
   hipGetDevice(&cur);
   size_t f = 0, t = 0;
   hipError_t he = hipSetDevice(device);
   if (he == hipSuccess) he = hipMemGetInfo(&f, &t);
   hipSetDevice(cur);
-  if (he != hipSuccess) return fail(MIC_E_HIP, "hipMemGetInfo: %s", hipGetErrorString(he));
+  if (he != hipSuccess) return mic_set_error(MIC_E_HIP, "hipMemGetInfo: %s", hipGetErrorString(he));
   *free_bytes = f; *total_bytes = t;
   return MIC_OK;
 }
 
 int mic_db_kernel_name(const mic_engine* e, char* buf, size_t cap) {
-  if (!e || !buf || cap < 2) return fail(MIC_E_INVALID, "bad argument");
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
+  if (!e || !buf || cap < 2) return mic_set_error(MIC_E_INVALID, "bad argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
   return mic_query_kernel_name(e->table, e->slot_class, buf, cap);
 }
 
@@ -1224,10 +1205,10 @@ int mic_db_kernel_name(const mic_engine* e, char* buf, size_t cap) {
 // the RESIDENT table, every k-mer of the images may land in it, so those devices get the whole images - and give them back as soon
 // as their last engine is built.
 int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const char* prefix, int key_bytes, uint32_t sampling) {
-  if (!engines || !n_engines || !prefix) return fail(MIC_E_INVALID, "null argument");
+  if (!engines || !n_engines || !prefix) return mic_set_error(MIC_E_INVALID, "null argument");
   for (size_t i = 0; i < n_engines; ++i) {
-    if (!engines[i]) return fail(MIC_E_INVALID, "null engine");
-    if (engines[i]->cfg.k != engines[0]->cfg.k) return fail(MIC_E_INVALID, "the engines differ in k");
+    if (!engines[i]) return mic_set_error(MIC_E_INVALID, "null engine");
+    if (engines[i]->cfg.k != engines[0]->cfg.k) return mic_set_error(MIC_E_INVALID, "the engines differ in k");
   }
   std::string p(prefix);
   FILE* fs = fopen((p + ".sz").c_str(), "rb");
@@ -1252,19 +1233,19 @@ int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const 
     t_prev = t;
   };
   do {
-    if (!fs) { rc = fail(MIC_E_IO, "Failed to open %s.sz", prefix); break; }
-    if (!fk) { rc = fail(MIC_E_IO, "Failed to open %s.ky", prefix); break; }
-    if (!fl) { rc = fail(MIC_E_IO, "Failed to open %s.lb", prefix); break; }
+    if (!fs) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.sz", prefix); break; }
+    if (!fk) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.ky", prefix); break; }
+    if (!fl) { rc = mic_set_error(MIC_E_IO, "Failed to open %s.lb", prefix); break; }
     fseeko(fs, 0, SEEK_END);
     const uint64_t htsize = (uint64_t)ftello(fs);
     fseeko(fs, 0, SEEK_SET);
     uint64_t z0 = 0, z1 = 0;
     if ((rc = check_shard(htsize, z0, z1))) break;
     if (key_bytes == 0) key_bytes = mic_key_bytes_rule(htsize, engines[0]->cfg.k);
-    if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) { rc = fail(MIC_E_INVALID, "key_bytes must be 2, 4 or 8"); break; }
+    if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) { rc = mic_set_error(MIC_E_INVALID, "key_bytes must be 2, 4 or 8"); break; }
     h_sz = (uint8_t*)malloc(htsize);
-    if (!h_sz) { rc = fail(MIC_E_NOMEM, "out of host memory for bucket sizes"); break; }
-    if (!read_file_parallel(fs, h_sz, htsize)) { rc = fail(MIC_E_IO, "short read on %s.sz", prefix); break; }
+    if (!h_sz) { rc = mic_set_error(MIC_E_NOMEM, "out of host memory for bucket sizes"); break; }
+    if (!read_file_parallel(fs, h_sz, htsize)) { rc = mic_set_error(MIC_E_IO, "short read on %s.sz", prefix); break; }
     // every engine's bucket range (the whole table unless mic_db_set_part cut a bucket-range layout); elements and non-empty
     // buckets in front of each cut from ONE pass over the sizes
     std::vector<uint64_t> cuts;
@@ -1300,7 +1281,7 @@ int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const 
     }
     for (Dev& dv : devs) {
       dv.el_lo = el_at[at(dv.lo)]; dv.el_hi = el_at[at(dv.hi)];
-      if (hipSetDevice(dv.device) != hipSuccess) { rc = fail(MIC_E_HIP, "hipSetDevice failed"); break; }
+      if (hipSetDevice(dv.device) != hipSuccess) { rc = mic_set_error(MIC_E_HIP, "hipSetDevice failed"); break; }
       for (size_t i : dv.eng) if (engines[i]->db_loaded) mic_db_unload(engines[i]);
       const uint64_t n_el = dv.el_hi - dv.el_lo;
       hipError_t he = hipMalloc(&dv.d_sz, dv.hi - dv.lo);
@@ -1309,7 +1290,7 @@ int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const 
       if (he != hipSuccess) {
         size_t fr = 0, tot = 0;
         hipMemGetInfo(&fr, &tot);
-        rc = fail(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation on device %d (%.1f GB of images for buckets [%llu, %llu), %.1f GB free of %.1f): %s",
+        rc = mic_set_error(he == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "DB image allocation on device %d (%.1f GB of images for buckets [%llu, %llu), %.1f GB free of %.1f): %s",
                   dv.device, ((dv.hi - dv.lo) + n_el * (double)(key_bytes + 2)) / 1e9, (unsigned long long)dv.lo, (unsigned long long)dv.hi, fr / 1e9, tot / 1e9, hipGetErrorString(he));
         break;
       }
@@ -1354,7 +1335,7 @@ int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const 
         dv.build_s = (tb.tv_sec - ta.tv_sec) + (tb.tv_nsec - ta.tv_nsec) / 1e9;
       });
     for (auto& t : th) t.join();
-    for (size_t d = 0; d < devs.size(); ++d) if (rcs[d]) { rc = fail(rcs[d], "%s", msgs[d].c_str()); break; }
+    for (size_t d = 0; d < devs.size(); ++d) if (rcs[d]) { rc = mic_set_error(rcs[d], "%s", msgs[d].c_str()); break; }
     if (timing)
       for (Dev& dv : devs) fprintf(stderr, "[load x%zu] device %d: %zu table(s) built in %.3f s\n", n_engines, dv.device, dv.eng.size(), dv.build_s);
     lap("tables built");
@@ -1373,32 +1354,32 @@ int mic_db_load_files_multi(mic_engine* const* engines, size_t n_engines, const 
 }
 
 int mic_batch_check(mic_engine* e, size_t batch, int* done) {
-  if (!e || batch >= e->batches.size() || !done) return fail(MIC_E_INVALID, "bad argument");
+  if (!e || batch >= e->batches.size() || !done) return mic_set_error(MIC_E_INVALID, "bad argument");
   Batch& B = e->batches[batch];
   if (!B.scheduled) { *done = 0; return MIC_OK; }
   hipError_t he = hipEventQuery(B.done);
   if (he == hipSuccess) *done = 1;
   else if (he == hipErrorNotReady) *done = 0;
-  else return fail(MIC_E_HIP, "hipEventQuery: %s", hipGetErrorString(he));
+  else return mic_set_error(MIC_E_HIP, "hipEventQuery: %s", hipGetErrorString(he));
   return MIC_OK;
 }
 
 int mic_thread_bind_near_device(mic_engine* e, int on) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   mic_bind_thread_near_device(e->device, on);
   return MIC_OK;
 }
 
 int mic_sync(mic_engine* e) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(hipDeviceSynchronize());
+  MIC_TRY(hipDeviceSynchronize());
   return MIC_OK;
 }
 
 int mic_batches_free(mic_engine* e) {
-  if (!e) return fail(MIC_E_INVALID, "null engine");
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
   int rc = set_device(e);
   if (rc) return rc;
   hipDeviceSynchronize();
@@ -1409,73 +1390,73 @@ int mic_batches_free(mic_engine* e) {
 // ---- device-resident entry points ---------------------------------------------------------------------
 int mic_query_device(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, size_t n_reads, uint32_t* d_results,
                      uint32_t* d_rows, void* stream) {
-  if (!e || !d_rp || !d_cont || !d_results) return fail(MIC_E_INVALID, "null argument");
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
-  if (n_reads > 0xFFFFFFF0ull) return fail(MIC_E_INVALID, "too many reads in one call");
-  if (((uintptr_t)d_cont & 3) || ((uintptr_t)d_rp & 3)) return fail(MIC_E_INVALID, "d_containers and d_reads_pointer must be 4-byte aligned");
+  if (!e || !d_rp || !d_cont || !d_results) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
+  if (n_reads > 0xFFFFFFF0ull) return mic_set_error(MIC_E_INVALID, "too many reads in one call");
+  if (((uintptr_t)d_cont & 3) || ((uintptr_t)d_rp & 3)) return mic_set_error(MIC_E_INVALID, "d_containers and d_reads_pointer must be 4-byte aligned");
   int rc = set_device(e);
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-  HIPTRY(hipMemsetAsync(e->d_flagged, 0, 4, s));
+  MIC_TRY(hipMemsetAsync(e->d_flagged, 0, 4, s));
   MicQueryArgs a;
   a.t = e->table; a.reads_ptr = d_rp; a.cont = d_cont; a.n_reads = (uint32_t)n_reads;
   a.row_words = e->cfg.row_words; a.results = d_results; a.rows = d_rows;
   a.flagged = e->d_flagged; a.flagged_cap = e->flagged_cap;
   if (e->table.side && n_reads > e->crowd_reads) {      // (first call, or a larger one: the engine's launches are one at a time)
-    HIPTRY(hipStreamSynchronize(s));
+    MIC_TRY(hipStreamSynchronize(s));
     if (e->d_crowd) { hipFree(e->d_crowd); e->d_crowd = nullptr; e->crowd_reads = 0; }
-    HIPTRY(hipMalloc(&e->d_crowd, mic_crowd_dims(n_reads).words * 4));
+    MIC_TRY(hipMalloc(&e->d_crowd, mic_crowd_dims(n_reads).words * 4));
     e->crowd_reads = n_reads;
   }
   mic_crowd_attach(a, e->table.side ? e->d_crowd : nullptr, e->crowd_reads);
-  HIPTRY(hipEventRecord(e->ev0, s));
-  HIPTRY(mic_launch_query(a, e->slot_class, e->n_cu, s));
-  HIPTRY(hipEventRecord(e->ev1, s));
+  MIC_TRY(hipEventRecord(e->ev0, s));
+  MIC_TRY(mic_launch_query(a, e->slot_class, e->n_cu, s));
+  MIC_TRY(hipEventRecord(e->ev1, s));
   e->timed = true;
   e->last_n_reads = n_reads;
   return MIC_OK;
 }
 
 int mic_last_query_ms(mic_engine* e, float* ms) {
-  if (!e || !ms) return fail(MIC_E_INVALID, "null argument");
-  if (!e->timed) return fail(MIC_E_STATE, "no query was launched");
-  HIPTRY(hipEventSynchronize(e->ev1));
-  HIPTRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
+  if (!e || !ms) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->timed) return mic_set_error(MIC_E_STATE, "no query was launched");
+  MIC_TRY(hipEventSynchronize(e->ev1));
+  MIC_TRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
   return MIC_OK;
 }
 
 int mic_last_crowd_stats(mic_engine* e, uint32_t out[4]) {
-  if (!e || !out) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !out) return mic_set_error(MIC_E_INVALID, "null argument");
   out[0] = out[1] = out[2] = out[3] = 0;
   if (!e->timed || !e->d_crowd || !e->table.side) return MIC_OK;
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(hipEventSynchronize(e->ev1));
-  HIPTRY(hipMemcpy(out, e->d_crowd, 16, hipMemcpyDeviceToHost));
+  MIC_TRY(hipEventSynchronize(e->ev1));
+  MIC_TRY(hipMemcpy(out, e->d_crowd, 16, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
 int mic_debug_fetch_crowd(mic_engine* e, uint32_t* out, size_t words, uint32_t caps[3]) {
-  if (!e || !out || !caps) return fail(MIC_E_INVALID, "null argument");
-  if (!e->d_crowd || !e->timed) return fail(MIC_E_STATE, "no work area");
+  if (!e || !out || !caps) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->d_crowd || !e->timed) return mic_set_error(MIC_E_STATE, "no work area");
   int rc = set_device(e);
   if (rc) return rc;
   const MicCrowdDims d = mic_crowd_dims(e->crowd_reads);
   caps[0] = d.pend_cap; caps[1] = d.item_cap; caps[2] = d.pool_cap;
-  HIPTRY(hipEventSynchronize(e->ev1));
-  HIPTRY(hipMemcpy(out, e->d_crowd, (words < d.words ? words : d.words) * 4, hipMemcpyDeviceToHost));
+  MIC_TRY(hipEventSynchronize(e->ev1));
+  MIC_TRY(hipMemcpy(out, e->d_crowd, (words < d.words ? words : d.words) * 4, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
 int mic_resolve_flagged_device(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, uint32_t* d_results,
                                uint32_t* d_rows, void* stream, size_t* n_resolved) {
-  if (!e || !d_rp || !d_cont || !d_results) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !d_rp || !d_cont || !d_results) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : e->stream;
   uint32_t nf = 0;
-  HIPTRY(hipMemcpyAsync(&nf, e->d_flagged, 4, hipMemcpyDeviceToHost, s));
-  HIPTRY(hipStreamSynchronize(s));
+  MIC_TRY(hipMemcpyAsync(&nf, e->d_flagged, 4, hipMemcpyDeviceToHost, s));
+  MIC_TRY(hipStreamSynchronize(s));
   if (n_resolved) *n_resolved = nf;
   if (!nf) return MIC_OK;
   if (nf > e->flagged_cap) {
@@ -1486,56 +1467,56 @@ int mic_resolve_flagged_device(mic_engine* e, const uint32_t* d_rp, const uint16
 }
 
 int mic_merge_rows_device(mic_engine* e, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, void* stream) {
-  if (!e || !a || !b || !out) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !a || !b || !out) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(mic_launch_merge_rows(a, b, out, e->cfg.row_words, n, nullptr, stream ? (hipStream_t)stream : e->stream));
+  MIC_TRY(mic_launch_merge_rows(a, b, out, e->cfg.row_words, n, nullptr, stream ? (hipStream_t)stream : e->stream));
   return MIC_OK;
 }
 
 int mic_result_from_rows_device(mic_engine* e, const uint32_t* rows, uint32_t* results, size_t n, void* stream) {
-  if (!e || !rows || !results) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !rows || !results) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(mic_launch_result_from_rows(rows, e->cfg.row_words, results, n, stream ? (hipStream_t)stream : e->stream));
+  MIC_TRY(mic_launch_result_from_rows(rows, e->cfg.row_words, results, n, stream ? (hipStream_t)stream : e->stream));
   return MIC_OK;
 }
 
 int mic_result_from_dense_device(mic_engine* e, const uint32_t* d_counts, const uint32_t* d_ids, size_t n_ids, uint32_t* d_results,
                                  uint32_t* d_rows, void* stream) {
-  if (!e || !d_counts || !d_results) return fail(MIC_E_INVALID, "null argument");
+  if (!e || !d_counts || !d_results) return mic_set_error(MIC_E_INVALID, "null argument");
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(mic_launch_dense_finish(d_counts, d_ids, n_ids, e->cfg.num_targets ? e->cfg.num_targets : 1, d_results, d_rows,
+  MIC_TRY(mic_launch_dense_finish(d_counts, d_ids, n_ids, e->cfg.num_targets ? e->cfg.num_targets : 1, d_results, d_rows,
                                  e->cfg.row_words, stream ? (hipStream_t)stream : e->stream));
   return MIC_OK;
 }
 
 int mic_probe_stats_device(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, size_t n_reads, uint64_t out[4]) {
-  if (!e || !d_rp || !d_cont || !out) return fail(MIC_E_INVALID, "null argument");
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
+  if (!e || !d_rp || !d_cont || !out) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
   int rc = set_device(e);
   if (rc) return rc;
   unsigned long long* d = nullptr;
   unsigned long long h[4] = {0, 0, 0, 0};
-  HIPTRY(hipMalloc(&d, 32));
+  MIC_TRY(hipMalloc(&d, 32));
   hipError_t he = hipMemsetAsync(d, 0, 32, e->stream);
   if (he == hipSuccess) he = mic_launch_probe_stats(e->table, e->slot_class, d_rp, d_cont, n_reads, d, e->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(h, d, 32, hipMemcpyDeviceToHost, e->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
   hipFree(d);
-  if (he != hipSuccess) return fail(MIC_E_HIP, "probe stats: %s", hipGetErrorString(he));
+  if (he != hipSuccess) return mic_set_error(MIC_E_HIP, "probe stats: %s", hipGetErrorString(he));
   for (int i = 0; i < 4; ++i) out[i] = h[i];
   return MIC_OK;
 }
 
 int mic_count_dense_device(mic_engine* e, const uint32_t* d_rp, const uint16_t* d_cont, const uint32_t* d_ids,
                            size_t n_ids, uint32_t* d_counts, void* stream) {
-  if (!e || !d_rp || !d_cont || !d_counts) return fail(MIC_E_INVALID, "null argument");
-  if (!e->db_loaded) return fail(MIC_E_STATE, "no database loaded");
+  if (!e || !d_rp || !d_cont || !d_counts) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
   int rc = set_device(e);
   if (rc) return rc;
-  HIPTRY(mic_launch_dense_count(e->table, e->slot_class, d_rp, d_cont, d_ids, n_ids, e->cfg.num_targets ? e->cfg.num_targets : 1,
+  MIC_TRY(mic_launch_dense_count(e->table, e->slot_class, d_rp, d_cont, d_ids, n_ids, e->cfg.num_targets ? e->cfg.num_targets : 1,
                                 d_counts, stream ? (hipStream_t)stream : e->stream));
   return MIC_OK;
 }

@@ -43,11 +43,6 @@
 #include <mutex>
 #include <vector>
 
-// engine services (mic_engine.hip)
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
-
 namespace {
 
 constexpr uint32_t GZ_CHUNK = 8192;       // compressed bytes per finder chunk: below the size of a block (gzip: 16 Ki symbols, 10-30 KB), so that

@@ -14,15 +14,6 @@
 
 #include <hipcub/hipcub.hpp>
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicHitmap* mic_engine_hitmap(mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
-#define HTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    rc = mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
 size_t mic_hitmap_tmp_bytes(size_t n_items) {
   size_t tb = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_items);
@@ -43,26 +34,26 @@ int mic_hitmap_run(const MicTable& t, int slot_class, int n_cu, const uint32_t* 
   const size_t arr = ((n_reads + 1) * 4 + 255) & ~(size_t)255, tmp = mic_hitmap_tmp_bytes(n_reads + 1);
   *n_words = 0;
   if (n_reads == 0) {
-    HTRY(hipMemsetAsync(d_offsets, 0, 4, s));
-    HTRY(hipStreamSynchronize(s));
+    MIC_TRY_DONE(hipMemsetAsync(d_offsets, 0, 4, s));
+    MIC_TRY_DONE(hipStreamSynchronize(s));
     return MIC_OK;
   }
   // a word per k-mer position and a separator per part at the most: fewer than 8 per container, so the 32-bit offsets cannot wrap
-  HTRY(hipMemcpyAsync(&n_cont, d_rp + n_reads, 4, hipMemcpyDeviceToHost, s));
-  HTRY(hipStreamSynchronize(s));
+  MIC_TRY_DONE(hipMemcpyAsync(&n_cont, d_rp + n_reads, 4, hipMemcpyDeviceToHost, s));
+  MIC_TRY_DONE(hipStreamSynchronize(s));
   if (n_cont >= (1u << 29)) {
     rc = mic_set_error(MIC_E_UNSUPPORTED, "hit maps: %u containers in one call may need more than 2^32 - 1 words: split the reads", n_cont);
     goto done;
   }
-  HTRY(hipMalloc(&d, arr + tmp));
-  HTRY(mic_launch_hitmap(t, slot_class, n_cu, d_rp, d_cont, n_reads, d_results, n_targets, nullptr, (uint32_t*)d, false, s));
-  HTRY(mic_hitmap_scan((char*)d + arr, tmp, (const uint32_t*)d, d_offsets, n_reads + 1, s));
-  HTRY(hipMemcpyAsync(&total, d_offsets + n_reads, 4, hipMemcpyDeviceToHost, s));
-  HTRY(hipStreamSynchronize(s));
+  MIC_TRY_DONE(hipMalloc(&d, arr + tmp));
+  MIC_TRY_DONE(mic_launch_hitmap(t, slot_class, n_cu, d_rp, d_cont, n_reads, d_results, n_targets, nullptr, (uint32_t*)d, false, s));
+  MIC_TRY_DONE(mic_hitmap_scan((char*)d + arr, tmp, (const uint32_t*)d, d_offsets, n_reads + 1, s));
+  MIC_TRY_DONE(hipMemcpyAsync(&total, d_offsets + n_reads, 4, hipMemcpyDeviceToHost, s));
+  MIC_TRY_DONE(hipStreamSynchronize(s));
   *n_words = total;
   if (d_words && total && total <= cap_words) {
-    HTRY(mic_launch_hitmap(t, slot_class, n_cu, d_rp, d_cont, n_reads, d_results, n_targets, d_offsets, d_words, true, s));
-    HTRY(hipStreamSynchronize(s));
+    MIC_TRY_DONE(mic_launch_hitmap(t, slot_class, n_cu, d_rp, d_cont, n_reads, d_results, n_targets, d_offsets, d_words, true, s));
+    MIC_TRY_DONE(hipStreamSynchronize(s));
   }
 done:
   if (d) { hipStreamSynchronize(s); hipFree(d); }

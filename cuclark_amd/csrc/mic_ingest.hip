@@ -32,23 +32,6 @@
 #include <thread>
 #include <vector>
 
-struct mic_engine;
-// engine internals this file needs (mic_engine.hip)
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-int mic_bind_thread_near_device(int device, int on);
-void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
-MicAbund* mic_engine_abund(mic_engine* e);
-MicRollup* mic_engine_rollup(mic_engine* e);
-MicDensity* mic_engine_density(mic_engine* e);
-MicKsketch* mic_engine_ksketch(mic_engine* e);
-MicSplit* mic_engine_split(mic_engine* e);
-MicHitmap* mic_engine_hitmap(mic_engine* e);
-uint32_t* mic_engine_min_quality(mic_engine* e);
-uint32_t* mic_engine_low_complexity(mic_engine* e);
-void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
-bool mic_peer_enable(int from, int to);
-
 namespace {
 
 enum { H_NLINES = 0, H_NREADS = 1, H_STATUS = 2, H_CSV_BYTES = 3, H_FLAGGED = 4, H_NEWLINES = 5, H_CONT = 6, H_WORDS = 8 };
@@ -758,8 +741,11 @@ static hipError_t wait_event(hipEvent_t ev) {
   return e;
 }
 
-#define ITRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+// one host wait of a batch: until `on` has done what was enqueued on it so far
+hipError_t wait_stream(Slot& s, hipStream_t on) {
+  const hipError_t e = hipEventRecord(s.ev, on);
+  return e != hipSuccess ? e : wait_event(s.ev);
+}
 
 // A slot is ONE device allocation and ONE pinned allocation carved into its arrays (a few hundred hipMalloc /
 // hipHostMalloc calls cost more than the first batches take): pass 1 adds the sizes up, pass 2 hands the pieces out.
@@ -841,9 +827,6 @@ void free_ingest(Ingest* g) {
     hipSetDevice(g->device);
     for (void* p : s.dev_allocs) hipFree(p);
     for (void* p : s.host_allocs) hipHostFree(p);
-    if (s.d_hm_words) hipFree(s.d_hm_words);
-    if (s.d_hm_text) hipFree(s.d_hm_text);
-    if (s.h_hm_text) hipHostFree(s.h_hm_text);
     if (s.ev) mic_event_put(s.ev);
     if (s.ev_up) mic_event_put(s.ev_up);
     if (s.ev_k) mic_event_put(s.ev_k);
@@ -904,6 +887,15 @@ int ensure_split_buffers(Ingest* g, Slot& s) {
 
 // the slot's hit-map buffers: the fixed arrays once; the word buffer for at least `words` words and the text buffer (with its pinned
 // twin) for at least `text` bytes - grown, never shrunk; what they held is not kept (the caller grows them before the pass that fills them)
+// A buffer that grows is in the slot's allocation lists like every other (free_ingest frees what the lists hold): the grown one is
+// pushed there, the outgrown one is given back with this (is_dev: dev_allocs and hipFree, else host_allocs and hipHostFree)
+template <typename T> void drop_alloc(Slot& s, T*& p, bool is_dev) {
+  if (!p) return;
+  std::vector<void*>& list = is_dev ? s.dev_allocs : s.host_allocs;
+  list.erase(std::remove(list.begin(), list.end(), (void*)p), list.end());
+  if (is_dev) hipFree(p); else hipHostFree(p);
+  p = nullptr;
+}
 size_t hitmap_scan64_bytes(size_t n_items) {
   size_t tb = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n_items);
@@ -938,16 +930,18 @@ int ensure_hitmap_buffers(Ingest* g, Slot& s, size_t words, size_t text) {
   }
   if (words > s.hm_words_cap) {
     const size_t cap = std::max(words + words / 2, (size_t)1024);
-    if (s.d_hm_words) { hipFree(s.d_hm_words); s.d_hm_words = nullptr; s.hm_words_cap = 0; }
+    drop_alloc(s, s.d_hm_words, true);
+    s.hm_words_cap = 0;
     void* d = nullptr;
     e = hipMalloc(&d, cap * 4);
     if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu hit-map words: %s", cap, hipGetErrorString(e));
+    s.dev_allocs.push_back(d);
     s.d_hm_words = (uint32_t*)d; s.hm_words_cap = cap;
   }
   if (text > s.hm_text_cap) {
     const size_t cap = (std::max(text + text / 4, (size_t)4096) + 255) & ~(size_t)255;
-    if (s.d_hm_text) { hipFree(s.d_hm_text); s.d_hm_text = nullptr; }
-    if (s.h_hm_text) { hipHostFree(s.h_hm_text); s.h_hm_text = nullptr; }
+    drop_alloc(s, s.d_hm_text, true);
+    drop_alloc(s, s.h_hm_text, false);
     s.hm_text_cap = 0;
     void* d = nullptr; void* h = nullptr;
     mic_bind_thread_near_device(g->device, 1);
@@ -956,6 +950,8 @@ int ensure_hitmap_buffers(Ingest* g, Slot& s, size_t words, size_t text) {
     if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu bytes of pinned memory for the hit-map text: %s", cap, hipGetErrorString(e));
     e = hipMalloc(&d, cap);
     if (e != hipSuccess) { hipHostFree(h); return mic_set_error(MIC_E_NOMEM, "ingest slot: %zu bytes of hit-map text: %s", cap, hipGetErrorString(e)); }
+    s.host_allocs.push_back(h);
+    s.dev_allocs.push_back(d);
     s.d_hm_text = (char*)d; s.h_hm_text = (char*)h; s.hm_text_cap = cap;
   }
   return MIC_OK;
@@ -1039,7 +1035,7 @@ int setup_peers(Ingest* g, Slot& s, mic_engine* const* group, size_t P, size_t o
     rc = mic_engine_table(group[p], &t, &sc, &ncu, &dev, &k, &nt);
     if (rc) return rc;
     q.eng = group[p]; q.device = dev; q.table_id = t.slots;
-    ITRY(hipSetDevice(dev));
+    MIC_TRY(hipSetDevice(dev));
     const bool own = p == owner;
     for (int pass = 0; pass < 2; ++pass) {          // pass 0 adds the sizes up, pass 1 hands the pieces out
       Arena a;
@@ -1060,18 +1056,18 @@ int setup_peers(Ingest* g, Slot& s, mic_engine* const* group, size_t P, size_t o
         if (e != hipSuccess) return mic_set_error(MIC_E_NOMEM, "table-sharded ingest slot: %zu bytes on device %d: %s", a.off, dev, hipGetErrorString(e));
       }
     }
-    ITRY(mic_event_get(&q.ev_q, false));
-    ITRY(mic_event_get(&q.ev_done, false));
-    if (s.timed) for (hipEvent_t& e : q.tv) ITRY(mic_event_get(&e, true));
+    MIC_TRY(mic_event_get(&q.ev_q, false));
+    MIC_TRY(mic_event_get(&q.ev_done, false));
+    if (s.timed) for (hipEvent_t& e : q.tv) MIC_TRY(mic_event_get(&e, true));
     if (own) { q.d_rp = s.d_rp; q.d_cont = s.d_cont; q.d_res = s.d_results; q.d_flagged = s.d_flagged; q.d_crowd = s.d_crowd; q.stream = s.stream; }
     else {
-      ITRY(mic_stream_get(&q.stream));
-      ITRY(hipMemsetAsync(q.d_cont, 0, (g->cont_cap + 192) * 2, q.stream));     // (the query kernel's read-ahead looks past the last read)
-      ITRY(hipStreamSynchronize(q.stream));
+      MIC_TRY(mic_stream_get(&q.stream));
+      MIC_TRY(hipMemsetAsync(q.d_cont, 0, (g->cont_cap + 192) * 2, q.stream));     // (the query kernel's read-ahead looks past the last read)
+      MIC_TRY(hipStreamSynchronize(q.stream));
     }
   }
-  ITRY(hipSetDevice(s.peers[owner].device));
-  if (!s.ev_pack) ITRY(mic_event_get(&s.ev_pack, false));
+  MIC_TRY(hipSetDevice(s.peers[owner].device));
+  if (!s.ev_pack) MIC_TRY(mic_event_get(&s.ev_pack, false));
   mic_peer_enable_engines(group, P);
   return MIC_OK;
 }
@@ -1086,41 +1082,41 @@ int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* 
   const size_t cont_n = std::min<size_t>(g->cont_cap + 192, (size_t)nb / 8 + 2 * ((size_t)nb / (size_t)(k + 1)) + 10 * (size_t)n + 128);
   const bool timed = s.timed;
   s.fan_bytes = s.x_bytes = 0;
-  ITRY(hipSetDevice(O.device));
-  ITRY(hipEventRecord(s.ev_pack, s.stream));
+  MIC_TRY(hipSetDevice(O.device));
+  MIC_TRY(hipEventRecord(s.ev_pack, s.stream));
   for (size_t p = 0; p < P; ++p) {
     Slot::Peer& q = s.peers[p];
     MicTable t; int sc, ncu, dev, kk; uint32_t nt;
     int rc = mic_engine_table(group[p], &t, &sc, &ncu, &dev, &kk, &nt);
     if (rc) return rc;
     if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded on engine %zu of the group", p);
-    ITRY(hipSetDevice(dev));
+    MIC_TRY(hipSetDevice(dev));
     if (p != owner) {
-      ITRY(hipStreamWaitEvent(q.stream, s.ev_pack, 0));
-      if (timed) ITRY(hipEventRecord(q.tv[0], q.stream));
-      ITRY(hipMemcpyPeerAsync(q.d_rp, dev, O.d_rp, O.device, ((size_t)n + 2) * 4, q.stream));
-      ITRY(hipMemcpyPeerAsync(q.d_cont, dev, O.d_cont, O.device, cont_n * 2, q.stream));
+      MIC_TRY(hipStreamWaitEvent(q.stream, s.ev_pack, 0));
+      if (timed) MIC_TRY(hipEventRecord(q.tv[0], q.stream));
+      MIC_TRY(hipMemcpyPeerAsync(q.d_rp, dev, O.d_rp, O.device, ((size_t)n + 2) * 4, q.stream));
+      MIC_TRY(hipMemcpyPeerAsync(q.d_cont, dev, O.d_cont, O.device, cont_n * 2, q.stream));
       s.fan_bytes += ((size_t)n + 2) * 4 + cont_n * 2;
-    } else if (timed) ITRY(hipEventRecord(q.tv[0], q.stream));
-    ITRY(hipMemsetAsync(q.d_flagged, 0, 4, q.stream));
-    if (timed) ITRY(hipEventRecord(q.tv[1], q.stream));
+    } else if (timed) MIC_TRY(hipEventRecord(q.tv[0], q.stream));
+    MIC_TRY(hipMemsetAsync(q.d_flagged, 0, 4, q.stream));
+    if (timed) MIC_TRY(hipEventRecord(q.tv[1], q.stream));
     MicQueryArgs qa;
     qa.t = t; qa.reads_ptr = q.d_rp; qa.cont = q.d_cont; qa.n_reads = n; qa.row_words = (uint32_t)rw; qa.results = q.d_res;
     qa.rows = q.d_rows; qa.flagged = q.d_flagged; qa.flagged_cap = kFlaggedCapI;
     mic_crowd_attach(qa, q.d_crowd, g->max_reads / 4 + 64);
-    ITRY(mic_launch_query(qa, sc, ncu, q.stream));
-    ITRY(hipEventRecord(q.ev_q, q.stream));
-    if (timed) ITRY(hipEventRecord(q.tv[2], q.stream));
+    MIC_TRY(mic_launch_query(qa, sc, ncu, q.stream));
+    MIC_TRY(hipEventRecord(q.ev_q, q.stream));
+    if (timed) MIC_TRY(hipEventRecord(q.tv[2], q.stream));
   }
   for (size_t j = 0; j < P; ++j) {
     Slot::Peer& q = s.peers[j];
     const size_t lo = (size_t)n * j / P, hi = (size_t)n * (j + 1) / P, len = hi - lo;
-    ITRY(hipSetDevice(q.device));
+    MIC_TRY(hipSetDevice(q.device));
     if (timed) {
       // measuring runs: the stream first waits for EVERY engine's rows, so that what tv[3] .. tv[4] brackets is the copies and the
       // merges alone and not the other engines' kernels (the product form below lets a copy start as soon as its source is written)
-      for (size_t p = 0; p < P; ++p) if (p != j) ITRY(hipStreamWaitEvent(q.stream, s.peers[p].ev_q, 0));
-      ITRY(hipEventRecord(q.tv[3], q.stream));
+      for (size_t p = 0; p < P; ++p) if (p != j) MIC_TRY(hipStreamWaitEvent(q.stream, s.peers[p].ev_q, 0));
+      MIC_TRY(hipEventRecord(q.tv[3], q.stream));
     }
     if (len) {
       // the running sum: this engine's own rows of the range, then the two spare buffers in turn (the partial rows stay as the
@@ -1131,30 +1127,30 @@ int group_query_issue(mic_engine* const* group, size_t P, size_t owner, Ingest* 
       for (size_t p = 0; p < P; ++p) {
         if (p == j) continue;
         uint32_t* in = q.d_gather + got * len * rw;
-        if (!timed) ITRY(hipStreamWaitEvent(q.stream, s.peers[p].ev_q, 0));
-        ITRY(hipMemcpyPeerAsync(in, q.device, s.peers[p].d_rows + lo * rw, s.peers[p].device, len * rw * 4, q.stream));
-        ITRY(mic_launch_merge_rows(cur, in, spare[c], (uint32_t)rw, len, nullptr, q.stream));
+        if (!timed) MIC_TRY(hipStreamWaitEvent(q.stream, s.peers[p].ev_q, 0));
+        MIC_TRY(hipMemcpyPeerAsync(in, q.device, s.peers[p].d_rows + lo * rw, s.peers[p].device, len * rw * 4, q.stream));
+        MIC_TRY(mic_launch_merge_rows(cur, in, spare[c], (uint32_t)rw, len, nullptr, q.stream));
         cur = spare[c]; c ^= 1; ++got;
         s.x_bytes += len * rw * 4;
       }
-      if (j == owner) ITRY(mic_launch_result_from_rows(cur, (uint32_t)rw, O.d_res + lo * 8, len, q.stream));
+      if (j == owner) MIC_TRY(mic_launch_result_from_rows(cur, (uint32_t)rw, O.d_res + lo * 8, len, q.stream));
       else {
-        ITRY(mic_launch_result_from_rows(cur, (uint32_t)rw, q.d_res, len, q.stream));
-        ITRY(hipMemcpyPeerAsync(O.d_res + lo * 8, O.device, q.d_res, q.device, len * 32, q.stream));
+        MIC_TRY(mic_launch_result_from_rows(cur, (uint32_t)rw, q.d_res, len, q.stream));
+        MIC_TRY(hipMemcpyPeerAsync(O.d_res + lo * 8, O.device, q.d_res, q.device, len * 32, q.stream));
         s.x_bytes += len * 32;
       }
       if (d_merged) {        // roll-up: the summed rows of the range go to the owner as well (64 bytes a read next to the 32 of its result)
-        ITRY(hipMemcpyPeerAsync(d_merged + lo * rw, O.device, cur, q.device, len * rw * 4, q.stream));
+        MIC_TRY(hipMemcpyPeerAsync(d_merged + lo * rw, O.device, cur, q.device, len * rw * 4, q.stream));
         if (j != owner) s.x_bytes += len * rw * 4;
       }
     }
-    if (timed) ITRY(hipEventRecord(q.tv[4], q.stream));
-    ITRY(hipEventRecord(q.ev_done, q.stream));
+    if (timed) MIC_TRY(hipEventRecord(q.tv[4], q.stream));
+    MIC_TRY(hipEventRecord(q.ev_done, q.stream));
   }
-  ITRY(hipSetDevice(O.device));
-  for (size_t j = 0; j < P; ++j) if (j != owner) ITRY(hipStreamWaitEvent(s.stream, s.peers[j].ev_done, 0));
+  MIC_TRY(hipSetDevice(O.device));
+  for (size_t j = 0; j < P; ++j) if (j != owner) MIC_TRY(hipStreamWaitEvent(s.stream, s.peers[j].ev_done, 0));
   group_overflow_kernel<<<(n + 255) / 256, 256, 0, s.stream>>>(O.d_res, n, s.d_flagged);
-  ITRY(hipGetLastError());
+  MIC_TRY(hipGetLastError());
   return MIC_OK;
 }
 
@@ -1226,9 +1222,6 @@ struct mic_pairs {
   int device = 0;
 };
 
-// the engine keeps one Ingest* (opaque to it): mic_engine.hip
-void** mic_engine_ingest_slot(mic_engine* e);
-
 extern "C" {
 
 int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char* const* target_names, uint32_t n_targets,
@@ -1239,7 +1232,7 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  ITRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   mic_ingest_free(e);
   Ingest* g = new Ingest();
   g->eng = e; g->device = dev;
@@ -1262,11 +1255,11 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
       names.insert(names.end(), s, s + strlen(s));
       off[i + 1] = (uint32_t)names.size();
     }
-    ITRY(hipMalloc(&g->d_tnames, names.size() + 16));
+    MIC_TRY(hipMalloc(&g->d_tnames, names.size() + 16));
     ingest_warm_kernel<<<1, 64>>>((uint32_t*)g->d_tnames);       // (loads this file's device code now, not with the first batch)
-    ITRY(hipMalloc(&g->d_tname_off, off.size() * 4));
-    if (!names.empty()) ITRY(hipMemcpy(g->d_tnames, names.data(), names.size(), hipMemcpyHostToDevice));
-    ITRY(hipMemcpy(g->d_tname_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    MIC_TRY(hipMalloc(&g->d_tname_off, off.size() * 4));
+    if (!names.empty()) MIC_TRY(hipMemcpy(g->d_tnames, names.data(), names.size(), hipMemcpyHostToDevice));
+    MIC_TRY(hipMemcpy(g->d_tname_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
   }
   g->slots.resize(n_slots);
   size_t tmp1 = 0, tmp2 = 0, tmp3 = 0;
@@ -1307,64 +1300,82 @@ int mic_ingest_classify(mic_engine* e, size_t slot_id, size_t n_bytes, int flags
   return mic_ingest_classify_group(&e, 1, 0, slot_id, n_bytes, flags, out);
 }
 
-int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t owner, size_t slot_id, size_t n_bytes, int flags,
-                              mic_ingest_result* out) {
+}  // extern "C"
+
+// ---- one batch through a slot: the stages of mic_ingest_classify_group (below), in the order it runs them -----------------------------
+namespace {
+
+// What every stage reads.  A stage returns an error code; one that hands the batch back to the host path sets out->status.
+struct BatchCtx {
+  Ingest* g = nullptr; Slot* s = nullptr; mic_engine* e = nullptr;      // the slot's engine: the owner of a table-sharded batch
+  MicTable t; int sc = 0, ncu = 0, dev = 0, k = 0; uint32_t nt = 0;     // mic_engine_table(e)
+  uint32_t n_reads = 0, nb = 0, gr = 0; int paired = 0, fasta = 0; uint32_t lpr = 4;   // gr: blocks of 256 over n_reads + 1 items; lpr: lines per FASTQ record
+  // e's base-quality threshold (pack_kernel<true, *>) and low-complexity level (lowc_kernel, pack_kernel<*, true>), 0: none; the modes; e's split setting
+  uint32_t c0 = 0, lc = 0; bool no_csv = false, roll = false, resident = false, hitmaps = false; MicSplit sp;
+  hipStream_t st = nullptr, up = nullptr, down = nullptr;               // the slot's stream; e's upload and download streams
+};
+
+// the slot's Ingest when it has slot `slot_id`, else nullptr with the error set
+Ingest* ingest_with_slot(mic_engine* e, size_t slot_id) {
+  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
+  if (!g || slot_id >= g->slots.size()) { mic_set_error(MIC_E_STATE, "ingest slots are not allocated"); return nullptr; }
+  return g;
+}
+
+// argument checks, every feature's "not supported with" rule, the slot's state cleared; b filled but for n_reads, gr and roll
+int begin_batch(mic_engine* const* group, size_t n_group, size_t owner, size_t slot_id, size_t n_bytes, int flags, mic_ingest_result* out,
+                BatchCtx& b) {
   if (!group || n_group == 0 || owner >= n_group) return mic_set_error(MIC_E_INVALID, "bad group");
   for (size_t p = 0; p < n_group; ++p) if (!group[p]) return mic_set_error(MIC_E_INVALID, "null engine in the group");
-  mic_engine* e = group[owner];
+  mic_engine* e = b.e = group[owner];
   // k-mer sketches count the k-mers of ONE engine's table behind ITS query: the table-sharded mode is not integrated
   if (n_group > 1) for (size_t p = 0; p < n_group; ++p) if (mic_engine_ksketch(group[p])->on)
     return mic_set_error(MIC_E_UNSUPPORTED, "k-mer sketches are started on an engine of a table-sharded group: not supported");
   // hit maps are the labels of ONE engine's table along the read: likewise
   if (n_group > 1) for (size_t p = 0; p < n_group; ++p) if (mic_engine_hitmap(group[p])->on)
     return mic_set_error(MIC_E_UNSUPPORTED, "hit maps are started on an engine of a table-sharded group: not supported");
-  const int paired = flags & MIC_INGEST_PAIRED;
-  const bool no_csv = (flags & MIC_INGEST_NO_CSV) != 0;
-  const uint32_t lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;      // lines per FASTQ record
+  b.paired = flags & MIC_INGEST_PAIRED; b.no_csv = (flags & MIC_INGEST_NO_CSV) != 0; b.lpr = (flags & MIC_INGEST_FASTQ_2LINE) ? 2u : 4u;
   if (!e || !out) return mic_set_error(MIC_E_INVALID, "null argument");
-  // the base-quality threshold of the slot's engine (0: none): four-line FASTQ is then packed by pack_kernel<true>
-  const uint32_t c0 = *mic_engine_min_quality(e);
-  if (c0 && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while a base-quality threshold is set: the quality lines are gone");
-  const MicSplit sp = *mic_engine_split(e);
-  if (sp.on && lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while read splitting is started: the quality lines are gone");
-  // the low-complexity level of the slot's engine (0: none): lowc_kernel marks the masked bases, pack_kernel<*, true> skips them
-  const uint32_t lc = *mic_engine_low_complexity(e);
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  b.c0 = *mic_engine_min_quality(e);
+  if (b.c0 && b.lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while a base-quality threshold is set: the quality lines are gone");
+  b.sp = *mic_engine_split(e);
+  if (b.sp.on && b.lpr == 2) return mic_set_error(MIC_E_INVALID, "MIC_INGEST_FASTQ_2LINE while read splitting is started: the quality lines are gone");
+  b.lc = *mic_engine_low_complexity(e);
+  Ingest* g = b.g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   if (n_bytes == 0 || n_bytes > g->max_bytes) return mic_set_error(MIC_E_INVALID, "batch of %zu bytes does not fit the slot (%zu)", n_bytes, g->max_bytes);
-  MicTable t; int sc, ncu, dev, k; uint32_t nt;
-  int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
+  int rc = mic_engine_table(e, &b.t, &b.sc, &b.ncu, &b.dev, &b.k, &b.nt);
   if (rc) return rc;
-  if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
-  ITRY(hipSetDevice(dev));
-  Slot& s = g->slots[slot_id];
+  if (!b.t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
+  MIC_TRY(hipSetDevice(b.dev));
+  Slot& s = *(b.s = &g->slots[slot_id]);
   s.ru_valid = false; s.split_valid = false; s.hm_valid = false;
-  const bool hitmaps = mic_engine_hitmap(e)->on;
-  if (hitmaps && (t.sharded || t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
+  b.hitmaps = mic_engine_hitmap(e)->on;
+  if (b.hitmaps && (b.t.sharded || b.t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
   memset(out, 0, sizeof(*out));
-  const bool resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
-  const uint8_t first = resident ? (uint8_t)((flags & MIC_INGEST_RESIDENT_FASTQ) == MIC_INGEST_RESIDENT_FASTQ ? '@' : '>') : s.h_raw[0];
+  b.resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
+  const uint8_t first = b.resident ? (uint8_t)((flags & MIC_INGEST_RESIDENT_FASTQ) == MIC_INGEST_RESIDENT_FASTQ ? '@' : '>') : s.h_raw[0];
   if (first != '>' && first != '@') { out->status = MIC_INGEST_FALLBACK | MIC_INGEST_ODD_RECORD; return MIC_OK; }
-  const int fasta = first == '>';
-  static const bool timing = getenv("MIC_INGEST_TIMING") != nullptr;
-  const double t0 = timing ? now_s() : 0;
-  hipStream_t st = s.stream;
-  const uint32_t nb = (uint32_t)n_bytes;
-  const uint32_t n_tiles = (nb + ING_TILE - 1) / ING_TILE;
-  // ---- phase 1: bytes -> lines -> number of records.  The upload runs on the engine's upload stream, the CSV comes
-  // back on its download stream (mic_engine.hip: one stream per direction keeps both directions of the link busy)
-  hipStream_t up, down;
-  mic_engine_copy_streams(e, &up, &down);
-  if (!resident) {
-    ITRY(hipMemcpyAsync(s.d_raw, s.h_raw, n_bytes, hipMemcpyHostToDevice, up));
-    ITRY(hipEventRecord(s.ev_up, up));
-    ITRY(hipStreamWaitEvent(st, s.ev_up, 0));
+  b.fasta = first == '>';
+  b.st = s.stream; b.nb = (uint32_t)n_bytes;
+  mic_engine_copy_streams(e, &b.up, &b.down);
+  return MIC_OK;
+}
+
+// phase 1: bytes -> lines -> number of records, the header to the host and the batch's first wait.  The upload runs on the engine's
+// upload stream, the CSV comes back on its download stream (mic_engine.hip: one stream per direction keeps both directions busy)
+int index_records(BatchCtx& b, mic_ingest_result* out) {
+  Ingest* g = b.g; Slot& s = *b.s; const hipStream_t st = b.st;
+  const uint32_t nb = b.nb, n_tiles = (nb + ING_TILE - 1) / ING_TILE, lpr = b.lpr; const int fasta = b.fasta;
+  if (!b.resident) {
+    MIC_TRY(hipMemcpyAsync(s.d_raw, s.h_raw, nb, hipMemcpyHostToDevice, b.up));
+    MIC_TRY(hipEventRecord(s.ev_up, b.up));
+    MIC_TRY(hipStreamWaitEvent(st, s.ev_up, 0));
   }
-  ITRY(hipMemsetAsync(s.d_hdr, 0, H_WORDS * 4, st));
+  MIC_TRY(hipMemsetAsync(s.d_hdr, 0, H_WORDS * 4, st));
   line_count_kernel<<<n_tiles, 256, 0, st>>>(s.d_raw, nb, s.d_tile);
-  ITRY(hipMemsetAsync(s.d_tile + n_tiles, 0, 4, st));
+  MIC_TRY(hipMemsetAsync(s.d_tile + n_tiles, 0, 4, st));
   size_t tb = s.tmp_bytes;
-  ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_tile, s.d_tile_off, (int)(n_tiles + 1), st));
+  MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_tile, s.d_tile_off, (int)(n_tiles + 1), st));
   line_start_kernel<<<n_tiles, 256, 0, st>>>(s.d_raw, nb, s.d_tile_off, s.d_line_start, (uint32_t)g->max_lines);
   lines_finish_kernel<<<1, 1, 0, st>>>(s.d_raw, nb, s.d_tile_off, n_tiles, s.d_line_start, (uint32_t)g->max_lines, fasta, lpr, (uint32_t)g->max_reads, s.d_hdr);
   if (fasta) {
@@ -1374,96 +1385,212 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
     const uint32_t gl = (n_scan + 255) / 256;
     fasta_flag_kernel<<<gl, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, s.d_hdr, (uint32_t)g->max_lines, n_scan, s.d_flag);
     tb = s.tmp_bytes;
-    ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_flag, s.d_rec_of_line, (int)n_scan, st));
+    MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_flag, s.d_rec_of_line, (int)n_scan, st));
     fasta_scatter_kernel<<<gl, 256, 0, st>>>(s.d_flag, s.d_rec_of_line, (uint32_t)g->max_lines, (uint32_t)g->max_reads, s.d_hdr_line, s.d_hdr);
   }
-  ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));
-  ITRY(hipEventRecord(s.ev, st));
-  ITRY(wait_event(s.ev));
-  const double t1 = timing ? now_s() : 0;
-  uint32_t n_reads = s.h_hdr[H_NREADS];
+  MIC_TRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));
+  MIC_TRY(wait_stream(s, st));
+  b.n_reads = s.h_hdr[H_NREADS]; b.gr = (b.n_reads + 1 + 255) / 256;
   out->n_lines = s.h_hdr[H_NLINES];
-  if (s.h_hdr[H_STATUS] || n_reads == 0) { out->status = MIC_INGEST_FALLBACK | s.h_hdr[H_STATUS]; return MIC_OK; }
-  // ---- phase 2: records -> packed reads -> query -> CSV line lengths
-  const uint32_t gr = (n_reads + 1 + 255) / 256;
-  if (fasta) record_kernel<true><<<gr, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, s.d_hdr_line, n_reads, lpr, k, s.rec, s.d_hdr);
-  else record_kernel<false><<<gr, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, nullptr, n_reads, lpr, k, s.rec, s.d_hdr);
-  tb = s.tmp_bytes;
-  ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.rec.bound, s.d_rp, (int)(n_reads + 1), st));
-  {
-    unsigned blocks = (n_reads + 3) / 4, cap = (unsigned)ncu * 64u;
-    if (blocks > cap) blocks = cap;
-    const bool qual = c0 && !fasta;
-    if (lc) {
-      if (!s.d_lowc) {   // the slot's first batch that is masked: one bit per byte of the slot's text; it goes with the slot
-        void* d = nullptr;
-        ITRY(hipMalloc(&d, g->max_bytes / 8 + 64));
-        s.dev_allocs.push_back(d);
-        s.d_lowc = (uint32_t*)d;
-      }
-      ITRY(hipMemsetAsync(s.d_lowc, 0, ((size_t)nb + 31) / 32 * 4, st));
-      if (qual) lowc_kernel<true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, n_reads, lc, s.d_line_start, c0, s.d_lowc);
-      else lowc_kernel<false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, n_reads, lc, nullptr, 0u, s.d_lowc);
-      if (qual) pack_kernel<true, true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0, s.d_lowc);
-      else pack_kernel<false, true><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u, s.d_lowc);
-    } else if (qual) pack_kernel<true, false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, s.d_line_start, c0, nullptr);
-    else pack_kernel<false, false><<<blocks, 256, 0, st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, n_reads, k, nullptr, 0u, nullptr);
-  }
-  // rank roll-up started on the slot's engine: the rows instantiation of the same kernel fills the slot's row buffer.  One engine:
-  // rows of the --extended width, so that a batch is handed back exactly when it is handed back without roll-up (a row that does
-  // not fit is a read of more than 64 targets, which the kernel flags anyway); a group: the summed rows, kGroupRowWords wide.
-  MicRollup& ru = *mic_engine_rollup(e);
-  const bool roll = ru.on && ru.d_counts && ru.n_levels;
-  if (roll && (rc = ensure_rollup_buffers(g, s, n_group == 1 ? std::min<uint32_t>(nt + 1, 65u) : kGroupRowWords))) return rc;
+  if (s.h_hdr[H_STATUS] || b.n_reads == 0) out->status = MIC_INGEST_FALLBACK | s.h_hdr[H_STATUS];
+  return MIC_OK;
+}
+
+// lowc_kernel (LOWC) and pack_kernel<QUAL, LOWC>: the arguments of the four instantiations in one place
+template <bool QUAL, bool LOWC>
+void launch_pack(const BatchCtx& b, unsigned blocks) {
+  Slot& s = *b.s; const uint32_t* line_start = QUAL ? s.d_line_start : nullptr; const uint32_t c0 = QUAL ? b.c0 : 0u;
+  if (LOWC) lowc_kernel<QUAL><<<blocks, 256, 0, b.st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, b.n_reads, b.lc, line_start, c0, s.d_lowc);
+  pack_kernel<QUAL, LOWC><<<blocks, 256, 0, b.st>>>(s.d_raw, s.rec.seq_s, s.rec.seq_e, s.d_rp, s.d_cont, b.n_reads, b.k, line_start, c0,
+                                                    LOWC ? s.d_lowc : nullptr);
+}
+
+// phase 2 begins: records -> packed reads
+int pack_reads(BatchCtx& b) {
+  Slot& s = *b.s; const hipStream_t st = b.st; const uint32_t n_reads = b.n_reads, nb = b.nb;
+  if (b.fasta) record_kernel<true><<<b.gr, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, s.d_hdr_line, n_reads, b.lpr, b.k, s.rec, s.d_hdr);
+  else record_kernel<false><<<b.gr, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, nullptr, n_reads, b.lpr, b.k, s.rec, s.d_hdr);
+  size_t tb = s.tmp_bytes;
+  MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.rec.bound, s.d_rp, (int)(n_reads + 1), st));
+  unsigned blocks = (n_reads + 3) / 4, cap = (unsigned)b.ncu * 64u;
+  if (blocks > cap) blocks = cap;
+  const bool qual = b.c0 && !b.fasta;
+  if (b.lc) {
+    if (!s.d_lowc) {   // the slot's first batch that is masked: one bit per byte of the slot's text; it goes with the slot
+      void* d = nullptr;
+      MIC_TRY(hipMalloc(&d, b.g->max_bytes / 8 + 64));
+      s.dev_allocs.push_back(d);
+      s.d_lowc = (uint32_t*)d;
+    }
+    MIC_TRY(hipMemsetAsync(s.d_lowc, 0, ((size_t)nb + 31) / 32 * 4, st));
+    qual ? launch_pack<true, true>(b, blocks) : launch_pack<false, true>(b, blocks);
+  } else qual ? launch_pack<true, false>(b, blocks) : launch_pack<false, false>(b, blocks);
+  return MIC_OK;
+}
+
+// the query: one engine's launch, or the exchange of a table-sharded group.  Rank roll-up started on the slot's engine: the rows
+// instantiation of the same kernel fills the slot's row buffer.  One engine: rows of the --extended width, so that a batch is handed
+// back exactly when it is handed back without roll-up (a row that does not fit is a read of more than 64 targets, which the kernel
+// flags anyway); a group: the summed rows, kGroupRowWords wide.
+int query_batch(BatchCtx& b, mic_engine* const* group, size_t n_group, size_t owner) {
+  Ingest* g = b.g; Slot& s = *b.s; const hipStream_t st = b.st; int rc;
+  const MicRollup& ru = *mic_engine_rollup(b.e);
+  const bool roll = b.roll = ru.on && ru.d_counts && ru.n_levels;
+  if (roll && (rc = ensure_rollup_buffers(g, s, n_group == 1 ? std::min<uint32_t>(b.nt + 1, 65u) : kGroupRowWords))) return rc;
   if (n_group == 1) {
-    ITRY(hipMemsetAsync(s.d_flagged, 0, 4, st));
+    MIC_TRY(hipMemsetAsync(s.d_flagged, 0, 4, st));
     MicQueryArgs qa;
-    qa.t = t; qa.reads_ptr = s.d_rp; qa.cont = s.d_cont; qa.n_reads = n_reads; qa.row_words = roll ? s.ru_row_words : 0; qa.results = s.d_results;
+    qa.t = b.t; qa.reads_ptr = s.d_rp; qa.cont = s.d_cont; qa.n_reads = b.n_reads; qa.row_words = roll ? s.ru_row_words : 0; qa.results = s.d_results;
     qa.rows = roll ? s.d_ru_rows : nullptr; qa.flagged = s.d_flagged; qa.flagged_cap = kFlaggedCapI;
     mic_crowd_attach(qa, s.d_crowd, g->max_reads / 4 + 64);
-    ITRY(mic_launch_query(qa, sc, ncu, st));
+    MIC_TRY(mic_launch_query(qa, b.sc, b.ncu, st));
   } else {
     // table-sharded: all engines of the group probe the batch against their parts, the rows are summed read-range owned
-    if ((rc = group_query(group, n_group, owner, g, s, n_reads, nb, k, roll ? s.d_ru_rows : nullptr))) return rc;
-    ITRY(hipSetDevice(dev));
+    if ((rc = group_query(group, n_group, owner, g, s, b.n_reads, b.nb, b.k, roll ? s.d_ru_rows : nullptr))) return rc;
+    MIC_TRY(hipSetDevice(b.dev));
   }
-  CsvArgs ca;
+  return MIC_OK;
+}
+
+CsvArgs csv_args(const BatchCtx& b) {
+  const Ingest* g = b.g; const Slot& s = *b.s; CsvArgs ca;
   ca.raw = s.d_raw; ca.name_s = s.rec.name_s; ca.name_len = s.rec.name_len; ca.length = s.rec.length; ca.results = s.d_results;
-  ca.tnames = g->d_tnames; ca.tname_off = g->d_tname_off; ca.n_targets = g->n_targets; ca.n_reads = n_reads; ca.k = k; ca.paired = paired ? 1 : 0;
+  ca.tnames = g->d_tnames; ca.tname_off = g->d_tname_off; ca.n_targets = g->n_targets; ca.n_reads = b.n_reads; ca.k = b.k; ca.paired = b.paired ? 1 : 0;
+  return ca;
+}
+
+// the CSV line lengths, their scan and the batch's status word - or the status word alone
+int csv_lengths(BatchCtx& b) {
+  Ingest* g = b.g; Slot& s = *b.s; const hipStream_t st = b.st; const uint32_t n_reads = b.n_reads;
   const uint32_t cont_cap = (uint32_t)std::min<size_t>(g->cont_cap, 0xFFFFFFFFu);
-  if (!no_csv) {
-    csv_len_kernel<<<gr, 256, 0, st>>>(ca, s.d_line_len, s.d_hdr);
-    tb = s.tmp_bytes;
-    ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_line_len, s.d_line_off, (int)(n_reads + 1), st));
+  if (!b.no_csv) {
+    csv_len_kernel<<<b.gr, 256, 0, st>>>(csv_args(b), s.d_line_len, s.d_hdr);
+    size_t tb = s.tmp_bytes;
+    MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_line_len, s.d_line_off, (int)(n_reads + 1), st));
     csv_finish_kernel<<<1, 1, 0, st>>>(s.d_line_off, n_reads, s.d_flagged, s.d_rp, (uint32_t)std::min<size_t>(g->csv_cap, 0xFFFFFFFFu), cont_cap, s.d_hdr);
   } else {
-    nocsv_status_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(s.d_results, s.rec.length, paired ? 1 : 0, k, n_reads, s.d_flagged, s.d_rp, cont_cap, s.d_hdr);
+    nocsv_status_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(s.d_results, s.rec.length, b.paired ? 1 : 0, b.k, n_reads, s.d_flagged, s.d_rp, cont_cap, s.d_hdr);
   }
-  {  // abundance counters of the slot's engine (the owner of a table-sharded batch): the kernel adds nothing when the status word says
-     // the batch goes back to the host path
-    MicAbund& ab = *mic_engine_abund(e);
-    if (ab.on && ab.d_counts && ab.n_words == nt + 2)
-      ITRY(mic_launch_abund(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ab, ab.d_counts, s.d_hdr + H_STATUS, st));
+  return MIC_OK;
+}
+
+// what is counted on the device for the slot's engine (the owner of a table-sharded batch): every kernel here adds nothing when the
+// status word says that the batch goes back to the host path
+int count_products(BatchCtx& b) {
+  Slot& s = *b.s; const hipStream_t st = b.st; const uint32_t* status = s.d_hdr + H_STATUS;
+  const uint32_t n_reads = b.n_reads, nt = b.nt, norm_sub = b.paired ? 1u : 0u; const int k = b.k;
+  const MicAbund& ab = *mic_engine_abund(b.e);
+  if (ab.on && ab.d_counts && ab.n_words == nt + 2)
+    MIC_TRY(mic_launch_abund(s.d_results, s.rec.length, norm_sub, n_reads, k, nt, ab, ab.d_counts, status, st));
+  if (b.roll) {
+    const MicRollup& ru = *mic_engine_rollup(b.e);
+    MIC_TRY(mic_launch_rollup(ru, s.d_ru_rows, s.ru_row_words, s.rec.length, norm_sub, n_reads, k, nt, ru.filter, s.d_rollup, nullptr, ru.d_counts, status, st));
+    if (s.h_rollup) MIC_TRY(hipMemcpyAsync(s.h_rollup, s.d_rollup, (size_t)n_reads * MIC_ROLLUP_WORDS * 4, hipMemcpyDeviceToHost, st));
   }
-  if (roll) {  // the same guard: nothing of a batch that is handed back is counted here
-    ITRY(mic_launch_rollup(ru, s.d_ru_rows, s.ru_row_words, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ru.filter, s.d_rollup, nullptr,
-                           ru.d_counts, s.d_hdr + H_STATUS, st));
-    if (s.h_rollup) ITRY(hipMemcpyAsync(s.h_rollup, s.d_rollup, (size_t)n_reads * MIC_ROLLUP_WORDS * 4, hipMemcpyDeviceToHost, st));
-  }
-  {  // score densities (mic_density_start on the slot's engine, the owner of a table-sharded batch), under the same status word
-    MicDensity& dn = *mic_engine_density(e);
-    if (dn.on && dn.d_counts)
-      ITRY(mic_launch_density(s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, ncu, dn.d_counts, s.d_hdr + H_STATUS, st));
-  }
-  {  // k-mer sketches (mic_ksketch_start on the slot's engine): a second probe pass over the reads that hit, under the same status word
-    MicKsketch& ks = *mic_engine_ksketch(e);
-    if (ks.on && ks.d_regs && ks.n_targets == nt)
-      ITRY(mic_launch_ksketch(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, ks.d_regs, ks.d_hits, s.d_hdr + H_STATUS, st));
-  }
-  if (no_csv && g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, st));
-  ITRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, st));
-  ITRY(hipEventRecord(s.ev, st));
-  ITRY(wait_event(s.ev));
+  const MicDensity& dn = *mic_engine_density(b.e);      // score densities (mic_density_start)
+  if (dn.on && dn.d_counts)
+    MIC_TRY(mic_launch_density(s.d_results, s.rec.length, norm_sub, n_reads, k, nt, b.ncu, dn.d_counts, status, st));
+  const MicKsketch& ks = *mic_engine_ksketch(b.e);      // k-mer sketches (mic_ksketch_start): a second probe pass over the reads that hit
+  if (ks.on && ks.d_regs && ks.n_targets == nt)
+    MIC_TRY(mic_launch_ksketch(b.t, b.sc, b.ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, ks.d_regs, ks.d_hits, status, st));
+  return MIC_OK;
+}
+
+// the tail of a product that goes to the host on the download stream: with a CSV, phase 3's wait for that stream covers the copy
+int wait_down_without_csv(const BatchCtx& b) {
+  if (b.no_csv) MIC_TRY(wait_stream(*b.s, b.down));
+  return MIC_OK;
+}
+
+// read splitting (mic_split_start on the slot's engine, the owner of a table-sharded batch), behind the status check: class and
+// length per record, one scan, the stable partition of the slot's text; then the classes asked for go to the slot's pinned buffer
+int split_product(BatchCtx& b) {
+  Slot& s = *b.s; const hipStream_t st = b.st; const MicSplit& sp = b.sp; const uint32_t n_reads = b.n_reads, nb = b.nb;
+  int rc = ensure_split_buffers(b.g, s);
+  if (rc) return rc;
+  MIC_TRY(mic_launch_split(s.d_raw, nb, s.rec.name_s, 1u, s.d_results, s.rec.length, b.paired ? 1u : 0u, n_reads, b.k, b.nt, sp.filter, sp.which,
+                           s.split_b, s.d_split, nullptr, st));
+  MIC_TRY(hipMemcpyAsync(s.h_split_tot, s.split_b.d_off2 + n_reads, 8, hipMemcpyDeviceToHost, st));
+  MIC_TRY(hipMemcpyAsync(s.h_split_tot + 1, s.split_b.d_ncls, 4, hipMemcpyDeviceToHost, st));
+  MIC_TRY(wait_stream(s, st));
+  const uint64_t n_cls = (uint32_t)s.h_split_tot[0], n_unc = s.h_split_tot[0] >> 32;      // bytes of the two classes
+  if (n_cls + n_unc > (uint64_t)nb + 1)
+    return mic_set_error(MIC_E_STATE, "split: %llu + %llu bytes from a text of %u", (unsigned long long)n_cls, (unsigned long long)n_unc, nb);
+  const uint64_t lo = (sp.which & MIC_SPLIT_CLASSIFIED) ? 0 : n_cls, hi = (sp.which & MIC_SPLIT_UNCLASSIFIED) ? n_cls + n_unc : n_cls;
+  if (hi > lo) MIC_TRY(hipMemcpyAsync(s.h_split + lo, s.d_split + lo, hi - lo, hipMemcpyDeviceToHost, b.down));   // (the partition is complete: the wait above)
+  if ((rc = wait_down_without_csv(b))) return rc;
+  s.split_which = sp.which; s.split_valid = true;
+  return MIC_OK;
+}
+
+// hit maps (mic_hitmap_start on the slot's engine), behind the status check like the split: words per read, their exclusive sum,
+// the words; line lengths, their exclusive sum, the lines.  The host reads the word total and later the text total (8 bytes
+// each) and grows the buffer that is too small before the pass that fills it.
+int hitmap_product(BatchCtx& b) {
+  Ingest* g = b.g; Slot& s = *b.s; const hipStream_t st = b.st;
+  const MicTable& t = b.t; const int sc = b.sc, ncu = b.ncu; const uint32_t n_reads = b.n_reads, nt = b.nt;
+  int rc = ensure_hitmap_buffers(g, s, 0, 0);
+  if (rc) return rc;
+  MIC_TRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, nullptr, s.d_hm_cnt, false, st));
+  MIC_TRY(mic_hitmap_scan(s.d_hm_tmp, s.hm_tmp_bytes, s.d_hm_cnt, s.d_hm_off, (size_t)n_reads + 1, st));
+  s.h_hm_tot[0] = 0;
+  MIC_TRY(hipMemcpyAsync(s.h_hm_tot, s.d_hm_off + n_reads, 4, hipMemcpyDeviceToHost, st));
+  MIC_TRY(wait_stream(s, st));
+  const size_t n_words = (size_t)s.h_hm_tot[0];
+  if ((rc = ensure_hitmap_buffers(g, s, n_words, 0))) return rc;
+  MIC_TRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, s.d_hm_off, s.d_hm_words, true, st));
+  HitmapTextArgs ha;
+  ha.raw = s.d_raw; ha.name_s = s.rec.name_s; ha.name_len = s.rec.name_len; ha.offsets = s.d_hm_off; ha.words = s.d_hm_words;
+  ha.tnames = g->d_tnames; ha.tname_off = g->d_tname_off; ha.n_targets = g->n_targets; ha.n_reads = n_reads;
+  hitmap_len_kernel<<<b.gr, 256, 0, st>>>(ha, s.d_hm_len);
+  size_t tb = s.hm_tmp_bytes;
+  MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_hm_tmp, tb, s.d_hm_len, s.d_hm_loff, (int)(n_reads + 1), st));
+  MIC_TRY(hipMemcpyAsync(s.h_hm_tot + 1, s.d_hm_loff + n_reads, 8, hipMemcpyDeviceToHost, st));
+  MIC_TRY(wait_stream(s, st));
+  const size_t n_text = (size_t)s.h_hm_tot[1];
+  if ((rc = ensure_hitmap_buffers(g, s, 0, n_text))) return rc;
+  hitmap_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ha, s.d_hm_loff, s.d_hm_text);
+  MIC_TRY(hipGetLastError());
+  MIC_TRY(hipEventRecord(s.ev_k, st));
+  MIC_TRY(hipStreamWaitEvent(b.down, s.ev_k, 0));
+  MIC_TRY(hipMemcpyAsync(s.h_hm_text, s.d_hm_text, n_text, hipMemcpyDeviceToHost, b.down));
+  if ((rc = wait_down_without_csv(b))) return rc;
+  s.hm_valid = true;
+  return MIC_OK;
+}
+
+// phase 3: CSV text -> host, and the batch's last wait
+int csv_to_host(BatchCtx& b, uint32_t csv_bytes) {
+  Slot& s = *b.s; const hipStream_t st = b.st, down = b.down;
+  csv_fmt_kernel<<<(b.n_reads + 255) / 256, 256, 0, st>>>(csv_args(b), s.d_line_off, s.d_csv);
+  MIC_TRY(hipGetLastError());
+  MIC_TRY(hipEventRecord(s.ev_k, st));
+  MIC_TRY(hipStreamWaitEvent(down, s.ev_k, 0));
+  MIC_TRY(hipMemcpyAsync(s.h_csv, s.d_csv, csv_bytes, hipMemcpyDeviceToHost, down));
+  if (b.g->want_results) MIC_TRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)b.n_reads * 32, hipMemcpyDeviceToHost, down));
+  MIC_TRY(wait_stream(s, down));
+  return MIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t owner, size_t slot_id, size_t n_bytes, int flags,
+                              mic_ingest_result* out) {
+  BatchCtx b;
+  int rc = begin_batch(group, n_group, owner, slot_id, n_bytes, flags, out, b);
+  if (rc || out->status) return rc;
+  static const bool timing = getenv("MIC_INGEST_TIMING") != nullptr;
+  const double t0 = timing ? now_s() : 0;
+  if ((rc = index_records(b, out)) || out->status) return rc;
+  const double t1 = timing ? now_s() : 0;
+  // ---- phase 2: records -> packed reads -> query -> CSV line lengths -> what is counted on the device
+  if ((rc = pack_reads(b)) || (rc = query_batch(b, group, n_group, owner)) || (rc = csv_lengths(b)) || (rc = count_products(b))) return rc;
+  Ingest* g = b.g; Slot& s = *b.s; const uint32_t n_reads = b.n_reads;
+  if (b.no_csv && g->want_results) MIC_TRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, b.st));
+  MIC_TRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, H_WORDS * 4, hipMemcpyDeviceToHost, b.st));
+  MIC_TRY(wait_stream(s, b.st));
   const double t2 = timing ? now_s() : 0;
   if (n_group > 1) group_harvest(g, s, n_reads);
   s.n_reads = n_reads; s.cont_used = s.h_hdr[H_CONT];
@@ -1471,85 +1598,18 @@ int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t o
   uint32_t status = s.h_hdr[H_STATUS];
   if (csv_bytes > g->csv_cap || s.h_hdr[H_CONT] > g->cont_cap) status |= MIC_INGEST_TOO_MANY;
   if (status) { out->status = MIC_INGEST_FALLBACK | status; return MIC_OK; }
-  s.ru_valid = roll && s.h_rollup;
-  if (sp.on) {
-    // read splitting (mic_split_start on the slot's engine, the owner of a table-sharded batch), behind the status check: class and
-    // length per record, one scan, the stable partition of the slot's text; then the classes asked for go to the slot's pinned buffer
-    if ((rc = ensure_split_buffers(g, s))) return rc;
-    ITRY(mic_launch_split(s.d_raw, nb, s.rec.name_s, 1u, s.d_results, s.rec.length, paired ? 1u : 0u, n_reads, k, nt, sp.filter, sp.which,
-                          s.split_b, s.d_split, nullptr, st));
-    ITRY(hipMemcpyAsync(s.h_split_tot, s.split_b.d_off2 + n_reads, 8, hipMemcpyDeviceToHost, st));
-    ITRY(hipMemcpyAsync(s.h_split_tot + 1, s.split_b.d_ncls, 4, hipMemcpyDeviceToHost, st));
-    ITRY(hipEventRecord(s.ev, st));
-    ITRY(wait_event(s.ev));
-    const uint64_t a = (uint32_t)s.h_split_tot[0], b = s.h_split_tot[0] >> 32;
-    if (a + b > (uint64_t)nb + 1) return mic_set_error(MIC_E_STATE, "split: %llu + %llu bytes from a text of %u", (unsigned long long)a, (unsigned long long)b, nb);
-    const uint64_t lo = (sp.which & MIC_SPLIT_CLASSIFIED) ? 0 : a, hi = (sp.which & MIC_SPLIT_UNCLASSIFIED) ? a + b : a;
-    if (hi > lo) ITRY(hipMemcpyAsync(s.h_split + lo, s.d_split + lo, hi - lo, hipMemcpyDeviceToHost, down));   // (the partition is complete: the wait above)
-    if (no_csv) {      // (with a CSV, phase 3's wait for the download stream covers this copy)
-      ITRY(hipEventRecord(s.ev, down));
-      ITRY(wait_event(s.ev));
-    }
-    s.split_which = sp.which; s.split_valid = true;
-  }
-  if (hitmaps) {
-    // hit maps (mic_hitmap_start on the slot's engine), behind the status check like the split: words per read, their exclusive sum,
-    // the words; line lengths, their exclusive sum, the lines.  The host reads the word total and later the text total (8 bytes
-    // each) and grows the buffer that is too small before the pass that fills it.
-    if ((rc = ensure_hitmap_buffers(g, s, 0, 0))) return rc;
-    ITRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, nullptr, s.d_hm_cnt, false, st));
-    ITRY(mic_hitmap_scan(s.d_hm_tmp, s.hm_tmp_bytes, s.d_hm_cnt, s.d_hm_off, (size_t)n_reads + 1, st));
-    s.h_hm_tot[0] = 0;
-    ITRY(hipMemcpyAsync(s.h_hm_tot, s.d_hm_off + n_reads, 4, hipMemcpyDeviceToHost, st));
-    ITRY(hipEventRecord(s.ev, st));
-    ITRY(wait_event(s.ev));
-    const size_t n_words = (size_t)s.h_hm_tot[0];
-    if ((rc = ensure_hitmap_buffers(g, s, n_words, 0))) return rc;
-    ITRY(mic_launch_hitmap(t, sc, ncu, s.d_rp, s.d_cont, n_reads, s.d_results, nt, s.d_hm_off, s.d_hm_words, true, st));
-    HitmapTextArgs ha;
-    ha.raw = s.d_raw; ha.name_s = s.rec.name_s; ha.name_len = s.rec.name_len; ha.offsets = s.d_hm_off; ha.words = s.d_hm_words;
-    ha.tnames = g->d_tnames; ha.tname_off = g->d_tname_off; ha.n_targets = g->n_targets; ha.n_reads = n_reads;
-    hitmap_len_kernel<<<gr, 256, 0, st>>>(ha, s.d_hm_len);
-    tb = s.hm_tmp_bytes;
-    ITRY(hipcub::DeviceScan::ExclusiveSum(s.d_hm_tmp, tb, s.d_hm_len, s.d_hm_loff, (int)(n_reads + 1), st));
-    ITRY(hipMemcpyAsync(s.h_hm_tot + 1, s.d_hm_loff + n_reads, 8, hipMemcpyDeviceToHost, st));
-    ITRY(hipEventRecord(s.ev, st));
-    ITRY(wait_event(s.ev));
-    const size_t n_text = (size_t)s.h_hm_tot[1];
-    if ((rc = ensure_hitmap_buffers(g, s, 0, n_text))) return rc;
-    hitmap_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ha, s.d_hm_loff, s.d_hm_text);
-    ITRY(hipGetLastError());
-    ITRY(hipEventRecord(s.ev_k, st));
-    ITRY(hipStreamWaitEvent(down, s.ev_k, 0));
-    ITRY(hipMemcpyAsync(s.h_hm_text, s.d_hm_text, n_text, hipMemcpyDeviceToHost, down));
-    if (no_csv) {      // (with a CSV, phase 3's wait for the download stream covers this copy)
-      ITRY(hipEventRecord(s.ev, down));
-      ITRY(wait_event(s.ev));
-    }
-    s.hm_valid = true;
-  }
-  if (no_csv) {
-    out->n_reads = n_reads; out->csv_bytes = 0; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
-    out->status = MIC_INGEST_OK;
-    if (timing) fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+count %.0f us, no csv\n", slot_id, nb, n_reads,
-                        (t1 - t0) * 1e6, (t2 - t1) * 1e6);
-    return MIC_OK;
-  }
-  // ---- phase 3: CSV text -> host
-  csv_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ca, s.d_line_off, s.d_csv);
-  ITRY(hipGetLastError());
-  ITRY(hipEventRecord(s.ev_k, st));
-  ITRY(hipStreamWaitEvent(down, s.ev_k, 0));
-  ITRY(hipMemcpyAsync(s.h_csv, s.d_csv, csv_bytes, hipMemcpyDeviceToHost, down));
-  if (g->want_results) ITRY(hipMemcpyAsync(s.h_results, s.d_results, (size_t)n_reads * 32, hipMemcpyDeviceToHost, down));
-  ITRY(hipEventRecord(s.ev, down));
-  ITRY(wait_event(s.ev));
-  out->n_reads = n_reads; out->csv_bytes = csv_bytes; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
+  s.ru_valid = b.roll && s.h_rollup;
+  // ---- the products behind the status check, then phase 3
+  if (b.sp.on && (rc = split_product(b))) return rc;
+  if (b.hitmaps && (rc = hitmap_product(b))) return rc;
+  if (!b.no_csv && (rc = csv_to_host(b, csv_bytes))) return rc;
+  out->n_reads = n_reads; out->csv_bytes = b.no_csv ? 0 : csv_bytes; out->csv = s.h_csv; out->results = g->want_results ? s.h_results : nullptr;
   out->status = MIC_INGEST_OK;
   if (timing) {
-    const double t3 = now_s();
-    fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+lengths %.0f us, csv %.0f us\n", slot_id, nb, n_reads,
-            (t1 - t0) * 1e6, (t2 - t1) * 1e6, (t3 - t2) * 1e6);
+    char csv_us[32] = "no csv";
+    if (!b.no_csv) snprintf(csv_us, sizeof(csv_us), "csv %.0f us", (now_s() - t2) * 1e6);
+    fprintf(stderr, "[ingest] slot %zu: %u bytes, %u reads: lines %.0f us, pack+query+%s %.0f us, %s\n", slot_id, b.nb, n_reads,
+            (t1 - t0) * 1e6, b.no_csv ? "count" : "lengths", (t2 - t1) * 1e6, csv_us);
   }
   return MIC_OK;
 }
@@ -1570,8 +1630,7 @@ int mic_ingest_set_low_complexity(mic_engine* e, uint32_t level) {
 
 int mic_ingest_rollup_rows(mic_engine* e, size_t slot_id, const uint32_t** rollup, uint64_t* n_reads) {
   if (!e || !rollup || !n_reads) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   const Slot& s = g->slots[slot_id];
   if (!s.ru_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no roll-up rows (mic_rollup_start, want_results, MIC_INGEST_OK)");
   *rollup = s.h_rollup; *n_reads = s.n_reads;
@@ -1581,8 +1640,7 @@ int mic_ingest_rollup_rows(mic_engine* e, size_t slot_id, const uint32_t** rollu
 int mic_ingest_split_text(mic_engine* e, size_t slot_id, const uint8_t** classified, uint64_t* classified_bytes, uint64_t* n_classified,
                           const uint8_t** unclassified, uint64_t* unclassified_bytes, uint64_t* n_unclassified) {
   if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   const Slot& s = g->slots[slot_id];
   if (!s.split_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no split text (mic_split_start, MIC_INGEST_OK)");
   const uint64_t a = (uint32_t)s.h_split_tot[0], b = s.h_split_tot[0] >> 32, nc = s.h_split_tot[1];
@@ -1598,8 +1656,7 @@ int mic_ingest_split_text(mic_engine* e, size_t slot_id, const uint8_t** classif
 
 int mic_ingest_hitmap_text(mic_engine* e, size_t slot_id, const uint8_t** text, uint64_t* bytes) {
   if (!e || !text || !bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   const Slot& s = g->slots[slot_id];
   if (!s.hm_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no hit-map text (mic_hitmap_start, MIC_INGEST_OK)");
   *text = (const uint8_t*)s.h_hm_text; *bytes = s.h_hm_tot[1];
@@ -1607,9 +1664,6 @@ int mic_ingest_hitmap_text(mic_engine* e, size_t slot_id, const uint8_t** text, 
 }
 
 // ---- paired-end texts on the device -------------------------------------------------------------------------------------
-#define PTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    rc = mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
 int mic_pairs_free(mic_engine* e, mic_pairs* p) {
   (void)e;
   if (!p) return MIC_OK;
@@ -1649,11 +1703,11 @@ int mic_pairs_index_device(mic_engine* e, const void* d_text1, size_t n1, const 
   { hipStream_t up_, down_; mic_engine_copy_streams(e, &up_, &down_); st = up_; }      // (a stream of its own would cost 2 ms to create)
   {
     size_t t0 = 0, t1 = 0;
-    PTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t0, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[0] + 1), st));
-    PTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[1] + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, t0, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[0] + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[1] + 1), st));
     tmp_bytes = std::max(t0, t1);
     const size_t a0 = up(((size_t)n_tiles[0] + 1) * 4), a1 = up(((size_t)n_tiles[1] + 1) * 4);
-    PTRY(hipMalloc(&p->d_scratch, 2 * a0 + 2 * a1 + 256 + up(tmp_bytes + 16)));
+    MIC_TRY_DONE(hipMalloc(&p->d_scratch, 2 * a0 + 2 * a1 + 256 + up(tmp_bytes + 16)));
     char* q = (char*)p->d_scratch;
     d_tile[0] = (uint32_t*)q; q += a0; d_tile_off[0] = (uint32_t*)q; q += a0;
     d_tile[1] = (uint32_t*)q; q += a1; d_tile_off[1] = (uint32_t*)q; q += a1;
@@ -1663,14 +1717,14 @@ int mic_pairs_index_device(mic_engine* e, const void* d_text1, size_t n1, const 
   lap("scratch allocated");
   for (int i = 0; i < 2; ++i) {
     line_count_kernel<<<n_tiles[i], 256, 0, st>>>(raw[i], nb[i], d_tile[i]);
-    PTRY(hipMemsetAsync(d_tile[i] + n_tiles[i], 0, 4, st));
+    MIC_TRY_DONE(hipMemsetAsync(d_tile[i] + n_tiles[i], 0, 4, st));
     size_t tb = tmp_bytes;
-    PTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile[i], d_tile_off[i], (int)(n_tiles[i] + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile[i], d_tile_off[i], (int)(n_tiles[i] + 1), st));
     text_facts_kernel<<<1, 1, 0, st>>>(raw[i], nb[i], d_tile_off[i], n_tiles[i], d_facts + 4 * i);
   }
-  PTRY(hipGetLastError());
-  PTRY(hipMemcpyAsync(facts, d_facts, 32, hipMemcpyDeviceToHost, st));
-  PTRY(hipStreamSynchronize(st));
+  MIC_TRY_DONE(hipGetLastError());
+  MIC_TRY_DONE(hipMemcpyAsync(facts, d_facts, 32, hipMemcpyDeviceToHost, st));
+  MIC_TRY_DONE(hipStreamSynchronize(st));
   for (int i = 0; i < 2; ++i) { nl[i] = facts[4 * i]; last[i] = (uint8_t)facts[4 * i + 1]; }
   lap("lines counted");
   for (int i = 0; i < 2; ++i) n_lines[i] = (uint64_t)nl[i] + (last[i] != '\n' ? 1 : 0);
@@ -1679,9 +1733,9 @@ int mic_pairs_index_device(mic_engine* e, const void* d_text1, size_t n1, const 
     const uint64_t n_rec = n_lines[0] / 4;
     p->n_rec = n_rec;
     const uint64_t n_samples = n_rec / p->stride + 2;
-    PTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(n_rec + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(n_rec + 1), st));
     const size_t b_ls = up((n_lines[0] + 2) * 4), b_off = up((n_rec + 1) * 8), b_smp = up(n_samples * 8);
-    PTRY(hipMalloc(&p->d_block, 2 * b_ls + 2 * b_off + b_smp + 256 + up(tmp2 + 16)));
+    MIC_TRY_DONE(hipMalloc(&p->d_block, 2 * b_ls + 2 * b_off + b_smp + 256 + up(tmp2 + 16)));
     char* q = (char*)p->d_block;
     p->d_ls[0] = (uint32_t*)q; q += b_ls; p->d_ls[1] = (uint32_t*)q; q += b_ls;
     p->d_off = (unsigned long long*)q; q += b_off;
@@ -1692,23 +1746,23 @@ int mic_pairs_index_device(mic_engine* e, const void* d_text1, size_t n1, const 
     lap("index block allocated");
     for (int i = 0; i < 2; ++i) {
       line_start_kernel<<<n_tiles[i], 256, 0, st>>>(raw[i], nb[i], d_tile_off[i], p->d_ls[i], (uint32_t)std::min<uint64_t>(n_lines[i] + 2, 0xFFFFFFFFull));
-      PTRY(hipGetLastError());
+      MIC_TRY_DONE(hipGetLastError());
       if (last[i] != '\n') {                   // the virtual line end of an unterminated last line (lines_finish_kernel's convention)
         nl[i] = nb[i] + 1;                     // (nl[] is done with; the source of an asynchronous copy has to outlive it)
-        PTRY(hipMemcpyAsync(p->d_ls[i] + n_lines[i], &nl[i], 4, hipMemcpyHostToDevice, st));
+        MIC_TRY_DONE(hipMemcpyAsync(p->d_ls[i] + n_lines[i], &nl[i], 4, hipMemcpyHostToDevice, st));
       }
       p->t[i].t = raw[i]; p->t[i].ls = p->d_ls[i]; p->t[i].nb = nb[i];
     }
-    PTRY(hipMemsetAsync(d_status, 0, 4, st));
+    MIC_TRY_DONE(hipMemsetAsync(d_status, 0, 4, st));
     pair_len_kernel<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(p->t[0], p->t[1], n_rec, d_mlen, d_status);
-    PTRY(hipGetLastError());
-    PTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_mlen, p->d_off, (int)(n_rec + 1), st));
+    MIC_TRY_DONE(hipGetLastError());
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_mlen, p->d_off, (int)(n_rec + 1), st));
     p->samples.resize(n_samples);
     pair_sample_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(p->d_off, n_rec, p->stride, n_samples, d_samples);
-    PTRY(hipGetLastError());
-    PTRY(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
-    PTRY(hipMemcpyAsync(status, d_status, 4, hipMemcpyDeviceToHost, st));
-    PTRY(hipStreamSynchronize(st));
+    MIC_TRY_DONE(hipGetLastError());
+    MIC_TRY_DONE(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
+    MIC_TRY_DONE(hipMemcpyAsync(status, d_status, 4, hipMemcpyDeviceToHost, st));
+    MIC_TRY_DONE(hipStreamSynchronize(st));
     lap("line starts, pair checks, offsets, samples");
   }
 done:
@@ -1735,8 +1789,7 @@ int mic_pairs_offsets(const mic_pairs* p, const uint64_t** samples, size_t* n_sa
 
 int mic_pairs_merge_to_slot(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r1, size_t slot_id, size_t* n_bytes) {
   if (!e || !p || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   unsigned long long o0, o1;
   if (r0 >= r1 || !pairs_offset(p, r0, o0) || !pairs_offset(p, r1, o1))
     return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
@@ -1745,10 +1798,10 @@ int mic_pairs_merge_to_slot(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r
   // it reads them through peer access
   if (g->device != p->device && !mic_peer_enable(g->device, p->device))
     return mic_set_error(MIC_E_UNSUPPORTED, "device %d has no peer access to device %d, where the inflated text lives", g->device, p->device);
-  ITRY(hipSetDevice(g->device));
+  MIC_TRY(hipSetDevice(g->device));
   Slot& s = g->slots[slot_id];
   launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, s.d_raw, *mic_engine_min_quality(e), s.stream);
-  ITRY(hipGetLastError());
+  MIC_TRY(hipGetLastError());
   *n_bytes = (size_t)(o1 - o0);
   return MIC_OK;
 }
@@ -1760,14 +1813,14 @@ int mic_pairs_text(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r1, void* 
     return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
   *n_bytes = (size_t)(o1 - o0);
   if (*n_bytes > cap) return mic_set_error(MIC_E_INVALID, "merged text of %zu bytes does not fit the buffer (%zu)", *n_bytes, cap);
-  ITRY(hipSetDevice(p->device));
+  MIC_TRY(hipSetDevice(p->device));
   uint8_t* d = nullptr;
-  ITRY(hipMalloc(&d, *n_bytes + 16));
+  MIC_TRY(hipMalloc(&d, *n_bytes + 16));
   launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, d, *mic_engine_min_quality(e), 0);
   hipError_t he = hipGetLastError();
   if (he == hipSuccess) he = hipMemcpy(host_dst, d, *n_bytes, hipMemcpyDeviceToHost);
   hipFree(d);
-  ITRY(he);
+  MIC_TRY(he);
   return MIC_OK;
 }
 
@@ -1820,23 +1873,23 @@ static int text_index(mic_engine* e, const void* d_text, size_t n, bool partial,
   size_t tmp_bytes = 0;
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   { hipStream_t up_, down_; mic_engine_copy_streams(e, &up_, &down_); st = up_; }      // (a stream of its own would cost 2 ms to create)
-  PTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles + 1), st));
+  MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles + 1), st));
   {
     const size_t a0 = up(((size_t)n_tiles + 1) * 4);
-    PTRY(hipMalloc(&p->d_scratch, 2 * a0 + 256 + up(tmp_bytes + 16)));
+    MIC_TRY_DONE(hipMalloc(&p->d_scratch, 2 * a0 + 256 + up(tmp_bytes + 16)));
     char* q = (char*)p->d_scratch;
     d_tile = (uint32_t*)q; q += a0; d_tile_off = (uint32_t*)q; q += a0; d_facts = (uint32_t*)q; q += 256; d_tmp = q;
   }
   line_count_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile, from);
-  PTRY(hipMemsetAsync(d_tile + n_tiles, 0, 4, st));
+  MIC_TRY_DONE(hipMemsetAsync(d_tile + n_tiles, 0, 4, st));
   {
     size_t tb = tmp_bytes;
-    PTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile, d_tile_off, (int)(n_tiles + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile, d_tile_off, (int)(n_tiles + 1), st));
   }
   text_facts_kernel<<<1, 1, 0, st>>>(raw, nb, d_tile_off, n_tiles, d_facts, from);
-  PTRY(hipGetLastError());
-  PTRY(hipMemcpyAsync(facts, d_facts, 16, hipMemcpyDeviceToHost, st));
-  PTRY(hipStreamSynchronize(st));
+  MIC_TRY_DONE(hipGetLastError());
+  MIC_TRY_DONE(hipMemcpyAsync(facts, d_facts, 16, hipMemcpyDeviceToHost, st));
+  MIC_TRY_DONE(hipStreamSynchronize(st));
   nl = facts[0]; last = (uint8_t)facts[1]; first = (uint8_t)facts[2];
   n_lines = (uint64_t)nl + (last != '\n' ? 1 : 0);
   if (partial) {
@@ -1850,33 +1903,33 @@ static int text_index(mic_engine* e, const void* d_text, size_t n, bool partial,
     p->fasta = true;
     const size_t b_ls = up((n_lines + 2) * 4), b_fl = up((n_lines + 1) * 4);
     size_t tmp2 = 0;
-    PTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_lines + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_lines + 1), st));
     if (n_lines >= 0x7FFFFFF0ull) { *status = PS_BIG; goto done; }
     // (the samples are sized by the lines - there are no more records than lines - and cut down once the count is known)
     const size_t b_smp = up((n_lines / p->stride + 2) * 8);
-    PTRY(hipMalloc(&p->d_block, b_ls + 2 * b_fl + b_smp + up(tmp2 + 16)));
+    MIC_TRY_DONE(hipMalloc(&p->d_block, b_ls + 2 * b_fl + b_smp + up(tmp2 + 16)));
     p->d_ls = (uint32_t*)p->d_block;
     uint32_t* d_flag = (uint32_t*)((char*)p->d_block + b_ls);
     uint32_t* d_rec = (uint32_t*)((char*)p->d_block + b_ls + b_fl);
     unsigned long long* d_samples = (unsigned long long*)((char*)p->d_block + b_ls + 2 * b_fl);
     void* d_tmp2 = (char*)p->d_block + b_ls + 2 * b_fl + b_smp;
     line_start_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile_off, p->d_ls, (uint32_t)(n_lines + 2), from);
-    PTRY(hipGetLastError());
-    if (last != '\n') { nl = nb + 1; PTRY(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
+    MIC_TRY_DONE(hipGetLastError());
+    if (last != '\n') { nl = nb + 1; MIC_TRY_DONE(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
     const unsigned gl = (unsigned)((n_lines + 1 + 255) / 256);
     text_fasta_flag_kernel<<<gl, 256, 0, st>>>(raw, nb, p->d_ls, n_lines, d_flag);
-    PTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_flag, d_rec, (int)(n_lines + 1), st));
+    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_flag, d_rec, (int)(n_lines + 1), st));
     uint32_t n_rec32 = 0;
-    PTRY(hipMemcpyAsync(&n_rec32, d_rec + n_lines, 4, hipMemcpyDeviceToHost, st));
+    MIC_TRY_DONE(hipMemcpyAsync(&n_rec32, d_rec + n_lines, 4, hipMemcpyDeviceToHost, st));
     text_fasta_sample_kernel<<<gl, 256, 0, st>>>(p->d_ls, d_flag, d_rec, n_lines, p->stride, d_samples);
-    PTRY(hipGetLastError());
-    PTRY(hipStreamSynchronize(st));
+    MIC_TRY_DONE(hipGetLastError());
+    MIC_TRY_DONE(hipStreamSynchronize(st));
     p->n_rec = n_rec32;
     if (n_rec32 == 0) { *status = PS_HEADER; goto done; }
     const uint64_t n_samples = p->n_rec / p->stride + 2;
     p->samples.assign(n_samples, (unsigned long long)nb);
     const uint64_t have = (p->n_rec + p->stride - 1) / p->stride;          // samples the kernel wrote: records 0, stride, ...
-    PTRY(hipMemcpy(p->samples.data(), d_samples, have * 8, hipMemcpyDeviceToHost));
+    MIC_TRY_DONE(hipMemcpy(p->samples.data(), d_samples, have * 8, hipMemcpyDeviceToHost));
     goto done;
   }
   if (first != '@') { *status = PS_HEADER; goto done; }                       // (anything else: the host path)
@@ -1886,17 +1939,17 @@ static int text_index(mic_engine* e, const void* d_text, size_t n, bool partial,
     p->n_rec = n_rec;
     const uint64_t n_samples = n_rec / p->stride + 2;
     const size_t b_ls = up((n_lines + 2) * 4), b_smp = up(n_samples * 8);
-    PTRY(hipMalloc(&p->d_block, b_ls + b_smp));
+    MIC_TRY_DONE(hipMalloc(&p->d_block, b_ls + b_smp));
     p->d_ls = (uint32_t*)p->d_block;
     unsigned long long* d_samples = (unsigned long long*)((char*)p->d_block + b_ls);
     line_start_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile_off, p->d_ls, (uint32_t)std::min<uint64_t>(n_lines + 2, 0xFFFFFFFFull), from);
-    PTRY(hipGetLastError());
-    if (last != '\n') { nl = nb + 1; PTRY(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
+    MIC_TRY_DONE(hipGetLastError());
+    if (last != '\n') { nl = nb + 1; MIC_TRY_DONE(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
     p->samples.resize(n_samples);
     text_sample_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(p->d_ls, nb, n_rec, p->stride, n_samples, d_samples);
-    PTRY(hipGetLastError());
-    PTRY(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
-    PTRY(hipStreamSynchronize(st));
+    MIC_TRY_DONE(hipGetLastError());
+    MIC_TRY_DONE(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
+    MIC_TRY_DONE(hipStreamSynchronize(st));
     *n_used = p->samples.back() - from;
   }
 done:
@@ -1923,18 +1976,17 @@ int mic_text_offsets(const mic_text* p, const uint64_t** samples, size_t* n_samp
 
 int mic_text_to_slot(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, size_t slot_id, size_t* n_bytes) {
   if (!e || !p || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   unsigned long long o0, o1;
   if (r0 >= r1 || !text_offset(p, r0, o0) || !text_offset(p, r1, o1))
     return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
   if (o1 - o0 > g->max_bytes) return mic_set_error(MIC_E_INVALID, "text of %llu bytes does not fit the slot (%zu)", o1 - o0, g->max_bytes);
-  ITRY(hipSetDevice(g->device));
+  MIC_TRY(hipSetDevice(g->device));
   Slot& s = g->slots[slot_id];
   if (g->device != p->device) {
     mic_peer_enable(g->device, p->device);      // (without peer access the runtime stages the copy through host memory)
-    ITRY(hipMemcpyPeerAsync(s.d_raw, g->device, p->t + o0, p->device, (size_t)(o1 - o0), s.stream));
-  } else ITRY(hipMemcpyAsync(s.d_raw, p->t + o0, (size_t)(o1 - o0), hipMemcpyDeviceToDevice, s.stream));
+    MIC_TRY(hipMemcpyPeerAsync(s.d_raw, g->device, p->t + o0, p->device, (size_t)(o1 - o0), s.stream));
+  } else MIC_TRY(hipMemcpyAsync(s.d_raw, p->t + o0, (size_t)(o1 - o0), hipMemcpyDeviceToDevice, s.stream));
   *n_bytes = (size_t)(o1 - o0);
   return MIC_OK;
 }
@@ -1946,26 +1998,25 @@ int mic_text_copy(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, void* ho
     return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
   *n_bytes = (size_t)(o1 - o0);
   if (*n_bytes > cap) return mic_set_error(MIC_E_INVALID, "text of %zu bytes does not fit the buffer (%zu)", *n_bytes, cap);
-  ITRY(hipSetDevice(p->device));
-  ITRY(hipMemcpy(host_dst, p->t + o0, *n_bytes, hipMemcpyDeviceToHost));
+  MIC_TRY(hipSetDevice(p->device));
+  MIC_TRY(hipMemcpy(host_dst, p->t + o0, *n_bytes, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
 int mic_ingest_fetch_packed(mic_engine* e, size_t slot_id, uint32_t* reads_pointer, size_t rp_cap, uint16_t* containers, size_t cont_cap,
                             uint64_t* n_reads, uint64_t* n_containers) {
   if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(e);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   Slot& s = g->slots[slot_id];
   if (n_reads) *n_reads = s.n_reads;
   if (n_containers) *n_containers = s.cont_used;
   if (reads_pointer) {
     if (rp_cap < (size_t)s.n_reads + 1) return mic_set_error(MIC_E_INVALID, "reads_pointer capacity too small");
-    ITRY(hipMemcpy(reads_pointer, s.d_rp, ((size_t)s.n_reads + 1) * 4, hipMemcpyDeviceToHost));
+    MIC_TRY(hipMemcpy(reads_pointer, s.d_rp, ((size_t)s.n_reads + 1) * 4, hipMemcpyDeviceToHost));
   }
   if (containers) {
     if (cont_cap < s.cont_used) return mic_set_error(MIC_E_INVALID, "containers capacity too small");
-    ITRY(hipMemcpy(containers, s.d_cont, (size_t)s.cont_used * 2, hipMemcpyDeviceToHost));
+    MIC_TRY(hipMemcpy(containers, s.d_cont, (size_t)s.cont_used * 2, hipMemcpyDeviceToHost));
   }
   return MIC_OK;
 }
@@ -1973,8 +2024,7 @@ int mic_ingest_fetch_packed(mic_engine* e, size_t slot_id, uint32_t* reads_point
 int mic_ingest_fetch_group_rows(mic_engine* owner, size_t slot_id, size_t part, uint32_t* rows, size_t cap_words, uint64_t* n_reads,
                                 uint32_t* row_words) {
   if (!owner) return mic_set_error(MIC_E_INVALID, "null engine");
-  Ingest* g = (Ingest*)*mic_engine_ingest_slot(owner);
-  if (!g || slot_id >= g->slots.size()) return mic_set_error(MIC_E_STATE, "ingest slots are not allocated");
+  Ingest* g = ingest_with_slot(owner, slot_id); if (!g) return MIC_E_STATE;
   Slot& s = g->slots[slot_id];
   if (part >= s.peers.size()) return mic_set_error(MIC_E_STATE, "the slot's last batch was not table-sharded over %zu parts", part + 1);
   if (n_reads) *n_reads = s.n_reads;
@@ -1982,9 +2032,9 @@ int mic_ingest_fetch_group_rows(mic_engine* owner, size_t slot_id, size_t part, 
   if (rows) {
     const size_t words = (size_t)s.n_reads * kGroupRowWords;
     if (cap_words < words) return mic_set_error(MIC_E_INVALID, "rows capacity too small");
-    ITRY(hipSetDevice(s.peers[part].device));
-    ITRY(hipMemcpy(rows, s.peers[part].d_rows, words * 4, hipMemcpyDeviceToHost));
-    ITRY(hipSetDevice(g->device));
+    MIC_TRY(hipSetDevice(s.peers[part].device));
+    MIC_TRY(hipMemcpy(rows, s.peers[part].d_rows, words * 4, hipMemcpyDeviceToHost));
+    MIC_TRY(hipSetDevice(g->device));
   }
   return MIC_OK;
 }

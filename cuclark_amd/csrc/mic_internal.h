@@ -315,4 +315,30 @@ hipError_t mic_launch_rollup(const MicRollup& ru, const uint32_t* rows, uint32_t
                              int k, uint32_t n_targets, const mic_abund_filter& f, uint32_t* rollup, uint32_t* levels,
                              unsigned long long* counts, const uint32_t* status, hipStream_t s);
 
+// ---- the engine as the other files of the library see it (mic_engine.hip defines all of this) --------------------------------------
+struct mic_engine;
+int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);   // slots == nullptr: no database
+int mic_set_error(int code, const char* fmt, ...);     // sets the thread's mic_last_error text, returns code
+int mic_bind_thread_near_device(int device, int on);   // the calling thread to the CPUs of the device's NUMA node, or back (on == 0); nests
+bool mic_peer_enable(int from, int to);                // device `from` reads device `to`'s memory directly; false: copies are staged
+void mic_peer_enable_engines(mic_engine* const* engines, size_t n);
+hipStream_t mic_engine_stream(mic_engine* e);
+void mic_engine_copy_streams(mic_engine* e, hipStream_t* up, hipStream_t* down);
+uint32_t mic_engine_row_words(const mic_engine* e);
+void** mic_engine_ingest_slot(mic_engine* e);          // the engine keeps one Ingest* (mic_ingest.hip), opaque to it
+MicAbund* mic_engine_abund(mic_engine* e);
+MicRollup* mic_engine_rollup(mic_engine* e);
+MicDensity* mic_engine_density(mic_engine* e);
+MicSplit* mic_engine_split(mic_engine* e);
+MicKsketch* mic_engine_ksketch(mic_engine* e);
+MicHitmap* mic_engine_hitmap(mic_engine* e);
+uint32_t* mic_engine_min_quality(mic_engine* e);
+uint32_t* mic_engine_low_complexity(mic_engine* e);
+
+// a failed HIP call sets the error text and returns its code / sets rc and jumps to the function's `done` label
+#define MIC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
+    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+#define MIC_TRY_DONE(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+    rc = mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
+
 #endif

@@ -7,15 +7,6 @@
 #include "mic_internal.h"
 #include "mic_ksketch.h"
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicKsketch* mic_engine_ksketch(mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
-#define KTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int mic_ksketch_start(mic_engine* e) {
@@ -24,23 +15,23 @@ int mic_ksketch_start(mic_engine* e) {
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
   if (nt == 0) return mic_set_error(MIC_E_STATE, "the engine has no targets");
-  KTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   MicKsketch& ks = *mic_engine_ksketch(e);
   const size_t reg_bytes = (size_t)nt * MIC_KSKETCH_REGS, bytes = reg_bytes + (size_t)nt * 8;
   if (ks.d_regs && ks.n_targets != nt) {          // (the engine's number of targets is fixed at creation: not reached)
-    KTRY(hipDeviceSynchronize());
-    KTRY(hipFree(ks.d_regs));
+    MIC_TRY(hipDeviceSynchronize());
+    MIC_TRY(hipFree(ks.d_regs));
     ks.d_regs = nullptr; ks.d_hits = nullptr;
   }
   if (!ks.d_regs) {
     void* d = nullptr;
-    KTRY(hipMalloc(&d, bytes));
+    MIC_TRY(hipMalloc(&d, bytes));
     ks.d_regs = (uint8_t*)d;
     ks.d_hits = (unsigned long long*)((uint8_t*)d + reg_bytes);      // (reg_bytes is a multiple of 16 KiB: aligned)
     ks.n_targets = nt;
   }
-  KTRY(hipDeviceSynchronize());             // (work still queued with the last run's sketching)
-  KTRY(hipMemset(ks.d_regs, 0, bytes));
+  MIC_TRY(hipDeviceSynchronize());             // (work still queued with the last run's sketching)
+  MIC_TRY(hipMemset(ks.d_regs, 0, bytes));
   ks.on = true;
   return MIC_OK;
 }
@@ -55,10 +46,10 @@ int mic_ksketch_fetch(mic_engine* e, uint8_t* regs, size_t n_regs, uint64_t* hit
   MicTable t; int sc, ncu, dev, k; uint32_t nt;
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
-  KTRY(hipSetDevice(dev));
-  KTRY(hipDeviceSynchronize());
-  KTRY(hipMemcpy(regs, ks.d_regs, n_regs, hipMemcpyDeviceToHost));
-  KTRY(hipMemcpy(hits, ks.d_hits, n_hits * 8, hipMemcpyDeviceToHost));
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipDeviceSynchronize());
+  MIC_TRY(hipMemcpy(regs, ks.d_regs, n_regs, hipMemcpyDeviceToHost));
+  MIC_TRY(hipMemcpy(hits, ks.d_hits, n_hits * 8, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 
@@ -78,9 +69,9 @@ int mic_ksketch_device(mic_engine* e, const uint32_t* d_reads_pointer, const uin
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
   if (!t.slots) return mic_set_error(MIC_E_STATE, "no database loaded");
-  KTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   hipStream_t s = stream ? (hipStream_t)stream : mic_engine_stream(e);
-  KTRY(mic_launch_ksketch(t, sc, ncu, d_reads_pointer, d_containers, n_reads, d_results, nt, d_regs, (unsigned long long*)d_hits, nullptr, s));
+  MIC_TRY(mic_launch_ksketch(t, sc, ncu, d_reads_pointer, d_containers, n_reads, d_results, nt, d_regs, (unsigned long long*)d_hits, nullptr, s));
   return MIC_OK;
 }
 

@@ -20,13 +20,6 @@
 
 #include <vector>
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicRollup* mic_engine_rollup(mic_engine* e);
-uint32_t mic_engine_row_words(const mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
 namespace {
 
 struct RollupArgs {
@@ -263,9 +256,6 @@ hipError_t mic_launch_rollup(const MicRollup& ru, const uint32_t* rows, uint32_t
   return hipGetLastError();
 }
 
-#define RTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 namespace {
 
 const char* kFilterMsg = "roll-up filter: denominators must be 10^0 .. 10^9 and numerators at most them";
@@ -300,10 +290,10 @@ int mic_rollup_set(mic_engine* e, uint32_t n_levels, const uint16_t* group_of) {
   MicRollup& ru = *mic_engine_rollup(e);
   if (ru.on) return mic_set_error(MIC_E_STATE, "roll-up counting is started on this engine: stop it before the lineage changes");
   if (n_levels && (rc = check_lineage(T, n_levels, group_of))) return rc;
-  RTRY(hipSetDevice(dev));
-  RTRY(hipDeviceSynchronize());
-  if (ru.d_block) { RTRY(hipFree(ru.d_block)); }
-  if (ru.d_counts) { RTRY(hipFree(ru.d_counts)); }
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipDeviceSynchronize());
+  if (ru.d_block) { MIC_TRY(hipFree(ru.d_block)); }
+  if (ru.d_counts) { MIC_TRY(hipFree(ru.d_counts)); }
   ru = MicRollup();
   if (n_levels == 0) return MIC_OK;
   // per level: the targets sorted by group (stable), and where each group's segment starts
@@ -323,7 +313,7 @@ int mic_rollup_set(mic_engine* e, uint32_t n_levels, const uint16_t* group_of) {
   }
   const size_t b_gof = ((size_t)n_levels * T * 2 + 255) & ~(size_t)255, b_seg = seg.size() * 4;
   char* d = nullptr;
-  RTRY(hipMalloc(&d, 2 * b_gof + b_seg));
+  MIC_TRY(hipMalloc(&d, 2 * b_gof + b_seg));
   hipError_t he = hipMemcpy(d, group_of, (size_t)n_levels * T * 2, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(d + b_gof, perm.data(), perm.size() * 2, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(d + 2 * b_gof, seg.data(), b_seg, hipMemcpyHostToDevice);
@@ -356,9 +346,9 @@ int mic_rollup_device(mic_engine* e, const uint32_t* d_rows, const uint32_t* d_n
   if (rc) return rc;
   const MicRollup& ru = *mic_engine_rollup(e);
   if (!ru.n_levels) return mic_set_error(MIC_E_STATE, "no lineage is set on this engine (mic_rollup_set)");
-  RTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   hipStream_t s = stream ? (hipStream_t)stream : mic_engine_stream(e);
-  RTRY(mic_launch_rollup(ru, d_rows, mic_engine_row_words(e), d_norm, 0, n_reads, k, nt, *filter, d_rollup, d_levels,
+  MIC_TRY(mic_launch_rollup(ru, d_rows, mic_engine_row_words(e), d_norm, 0, n_reads, k, nt, *filter, d_rollup, d_levels,
                          (unsigned long long*)d_counts, nullptr, s));
   return MIC_OK;
 }
@@ -375,14 +365,14 @@ int mic_rollup_dense_device(mic_engine* e, const uint32_t* d_dense, const uint32
   const MicRollup& ru = *mic_engine_rollup(e);
   if (!ru.n_levels) return mic_set_error(MIC_E_STATE, "no lineage is set on this engine (mic_rollup_set)");
   if (n_ids == 0) return MIC_OK;
-  RTRY(hipSetDevice(dev));
+  MIC_TRY(hipSetDevice(dev));
   DenseArgs a;
   a.dense = d_dense; a.ids = d_ids; a.norm = d_norm; a.perm = ru.d_perm; a.seg = ru.d_seg; a.rollup = d_rollup; a.levels = d_levels;
   a.counts = (unsigned long long*)d_counts; a.n_targets = nt; a.n_levels = ru.n_levels; a.k = k;
   for (int l = 0; l < 8; ++l) { a.n_groups[l] = ru.n_groups[l]; a.off[l] = ru.off[l]; a.seg_off[l] = ru.seg_off[l]; }
   a.f = *filter;
   rollup_dense_kernel<<<(unsigned)n_ids, 256, 0, stream ? (hipStream_t)stream : mic_engine_stream(e)>>>(a);
-  RTRY(hipGetLastError());
+  MIC_TRY(hipGetLastError());
   return MIC_OK;
 }
 
@@ -394,10 +384,10 @@ int mic_rollup_start(mic_engine* e, const mic_abund_filter* filter) {
   if (rc) return rc;
   MicRollup& ru = *mic_engine_rollup(e);
   if (!ru.n_levels) return mic_set_error(MIC_E_STATE, "no lineage is set on this engine (mic_rollup_set)");
-  RTRY(hipSetDevice(dev));
-  if (!ru.d_counts) RTRY(hipMalloc(&ru.d_counts, (size_t)ru.n_counters * 8));
-  RTRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
-  RTRY(hipMemset(ru.d_counts, 0, (size_t)ru.n_counters * 8));
+  MIC_TRY(hipSetDevice(dev));
+  if (!ru.d_counts) MIC_TRY(hipMalloc(&ru.d_counts, (size_t)ru.n_counters * 8));
+  MIC_TRY(hipDeviceSynchronize());             // (work still queued with the last run's counting)
+  MIC_TRY(hipMemset(ru.d_counts, 0, (size_t)ru.n_counters * 8));
   ru.filter = *filter;
   ru.on = true;
   return MIC_OK;
@@ -411,9 +401,9 @@ int mic_rollup_fetch(mic_engine* e, uint64_t* counts, size_t n) {
   int dev, k; uint32_t nt;
   int rc = engine_ctx(e, &dev, &k, &nt);
   if (rc) return rc;
-  RTRY(hipSetDevice(dev));
-  RTRY(hipDeviceSynchronize());
-  RTRY(hipMemcpy(counts, ru.d_counts, n * 8, hipMemcpyDeviceToHost));
+  MIC_TRY(hipSetDevice(dev));
+  MIC_TRY(hipDeviceSynchronize());
+  MIC_TRY(hipMemcpy(counts, ru.d_counts, n * 8, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 

@@ -15,12 +15,6 @@
 
 #include <hipcub/hipcub.hpp>
 
-struct mic_engine;
-int mic_engine_table(mic_engine* e, MicTable* t, int* slot_class, int* n_cu, int* device, int* k, uint32_t* n_targets);
-int mic_set_error(int code, const char* fmt, ...);
-MicSplit* mic_engine_split(mic_engine* e);
-hipStream_t mic_engine_stream(mic_engine* e);
-
 namespace {
 
 __global__ void __launch_bounds__(256) split_class_kernel(const uint8_t* __restrict__ text, uint32_t nb, const uint32_t* __restrict__ starts,
@@ -111,9 +105,6 @@ hipError_t mic_launch_split(const uint8_t* text, uint32_t nb, const uint32_t* st
   return hipGetLastError();
 }
 
-#define STRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    rc = mic_set_error(e_ == hipErrorOutOfMemory ? MIC_E_NOMEM : MIC_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
 extern "C" {
 
 int mic_split_start(mic_engine* e, const mic_abund_filter* filter, int which) {
@@ -147,15 +138,15 @@ int mic_split_device(mic_engine* e, const uint8_t* d_text, size_t nb, const uint
   MicSplitBufs b;
   const size_t arr = ((n_reads + 1) * 8 + 255) & ~(size_t)255;
   unsigned long long tot = 0; uint32_t ncls = 0;
-  STRY(hipSetDevice(dev));
+  MIC_TRY_DONE(hipSetDevice(dev));
   b.tmp_bytes = mic_split_tmp_bytes(n_reads + 1);
-  STRY(hipMalloc(&d, 2 * arr + 256 + b.tmp_bytes));
+  MIC_TRY_DONE(hipMalloc(&d, 2 * arr + 256 + b.tmp_bytes));
   b.d_len2 = (unsigned long long*)d; b.d_off2 = (unsigned long long*)((char*)d + arr);
   b.d_ncls = (uint32_t*)((char*)d + 2 * arr); b.d_tmp = (char*)d + 2 * arr + 256;
-  STRY(mic_launch_split(d_text, (uint32_t)nb, d_rec_start, 0, d_results, d_norm, 0, (uint32_t)n_reads, k, nt, *filter, which, b, d_out, nullptr, s));
-  STRY(hipMemcpyAsync(&tot, b.d_off2 + n_reads, 8, hipMemcpyDeviceToHost, s));
-  STRY(hipMemcpyAsync(&ncls, b.d_ncls, 4, hipMemcpyDeviceToHost, s));
-  STRY(hipStreamSynchronize(s));
+  MIC_TRY_DONE(mic_launch_split(d_text, (uint32_t)nb, d_rec_start, 0, d_results, d_norm, 0, (uint32_t)n_reads, k, nt, *filter, which, b, d_out, nullptr, s));
+  MIC_TRY_DONE(hipMemcpyAsync(&tot, b.d_off2 + n_reads, 8, hipMemcpyDeviceToHost, s));
+  MIC_TRY_DONE(hipMemcpyAsync(&ncls, b.d_ncls, 4, hipMemcpyDeviceToHost, s));
+  MIC_TRY_DONE(hipStreamSynchronize(s));
   totals[0] = (uint32_t)tot; totals[1] = tot >> 32; totals[2] = ncls; totals[3] = n_reads - ncls;
 done:
   if (d) { hipStreamSynchronize(s); hipFree(d); }
