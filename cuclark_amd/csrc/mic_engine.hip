@@ -737,6 +737,19 @@ int mic_db_get_info(const mic_engine* e, mic_db_info* info) {
   return MIC_OK;
 }
 
+int mic_debug_fetch_slots(mic_engine* e, uint64_t first, uint64_t n, uint32_t* out) {
+  if (!e || !out) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
+  if (e->table.layout != 2 || e->table.parted) return mic_set_error(MIC_E_UNSUPPORTED, "slots are fetched from a whole super-k-mer table only");
+  if (first > e->info.n_slots || n > e->info.n_slots - first) return mic_set_error(MIC_E_INVALID, "slots [%llu, +%llu) of %llu",
+                                                                                   (unsigned long long)first, (unsigned long long)n, (unsigned long long)e->info.n_slots);
+  int rc = set_device(e);
+  if (rc) return rc;
+  MIC_TRY(hipDeviceSynchronize());
+  if (n) MIC_TRY(hipMemcpy(out, e->table.slots + first * 8, n * 128, hipMemcpyDeviceToHost));
+  return MIC_OK;
+}
+
 const char* mic_db_last_build_report(void) {
   static thread_local std::string copy;
   std::lock_guard<std::mutex> lk(g_report_mu);

@@ -29,6 +29,18 @@
 #ifndef MIC_X
 #define MIC_X 0          /* measuring builds (tools/ablate_r6.sh): 1 no marker test, 2 no hand-over of crowded runs, 4 no spill of their reads' rows - 7: what the crowded path costs every read */
 #endif
+/* Round 11 (make variant VARIANT_FLAGS=-DMIC_X=.., tools/entry_walk_counters.py; results are WRONG with 16 .. 128, only counters and
+ * time are read): 8 three device counters of the entry walk (mic_debug_entry_walk), 16 no tally, 32 no loop control and no second pass, 64 no continuation test, 128 no result
+ * row, 256 the walk of the rounds before 11 (it goes on to entry e + 1 to find out that its key is another). */
+#if MIC_X & 8
+__device__ unsigned long long g_entry_walk[3];    // rounds, rounds with a second pass over the entries, second passes with hits
+extern "C" int mic_debug_entry_walk(unsigned long long out[3], int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_entry_walk), sizeof(g_entry_walk)) != hipSuccess) return -1;
+  const unsigned long long z[3] = {0, 0, 0};
+  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_entry_walk), z, sizeof(z)) != hipSuccess) return -1;
+  return 0;
+}
+#endif
 
 namespace {
 
@@ -254,7 +266,7 @@ __device__ __forceinline__ void finish_read(const RowAcc& acc, uint32_t n_ent, u
     }
   }
   if (overflow) flags |= MIC_FLAG_ROW_OVERFLOW_;
-  if (lane == 0) {
+  if (lane == 0 && !(MIC_X & 128)) {
     uint4 lo, hi;
     lo.x = total;
     lo.y = vbl;   // label+1
@@ -1216,6 +1228,15 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_s
 // counted twice; nucleotides outside the read part take part in the comparison only beyond the run's own range of j.
 // =====================================================================================================================
 __device__ __forceinline__ uint64_t wballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// v_writelane_b32: `value` (a scalar) into lane `lane` (a scalar) of `old`.  Where the compiler has no builtin for it the intrinsic is
+// declared under its LLVM name - a name with the overload's suffix and no symbol prefix, i.e. compiler internals: should an update
+// change it, the call no longer resolves and the build fails at the device link (it cannot go wrong silently: there is no such
+// function anywhere).  Worth about 3 VALU per new row entry.
+#if defined(__has_builtin) && __has_builtin(__builtin_amdgcn_writelane)
+__device__ __forceinline__ int mic_writelane(int value, int lane, int old) { return __builtin_amdgcn_writelane(value, lane, old); }
+#else
+extern "C" __device__ int mic_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+#endif
 
 static_assert(MIC_RMAX <= 32, "tally_counts sums the first two rows of lanes");
 #define MIC_R_CROWDED (-16)     /* `remaining` of a run that met the marker of a crowded minimizer: negative (a count never is), an inline constant */
@@ -1240,7 +1261,17 @@ __device__ __forceinline__ void tally_counts(uint32_t lab1, uint32_t cnt, RowAcc
       sum = __builtin_amdgcn_readlane(v, 15) + __builtin_amdgcn_readlane(v, 31);
     }
     total += sum;
-    row_add(acc, n_ent, overflow, l1, sum, lane);
+    // row_add, the new entry put into lane n_ent by two v_writelane (round 11): label and sum are scalars and so is the lane - the
+    // compare of the lane number, the two moves of the scalars into vector registers and the two selects are not needed
+    if (wballot(acc.label1 == l1)) {
+      if (acc.label1 == l1) acc.count += sum;
+    } else if (n_ent < 64) {
+      acc.label1 = (uint32_t)mic_writelane((int)l1, (int)n_ent, (int)acc.label1);
+      acc.count = (uint32_t)mic_writelane((int)sum, (int)n_ent, (int)acc.count);
+      ++n_ent;
+    } else {
+      overflow = 1;
+    }
   }
 }
 
@@ -1269,15 +1300,16 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
   // read-ahead through LDS: see query_kernel_s
   uint32_t* ahead0 = s_ahead[wv][0];
   uint32_t* ahead1 = s_ahead[wv][1];
-  auto ahead_issue = [&](uint32_t* entry, uint32_t pp_w, uint32_t r_ptr) {
+  // (ln: an opaque copy of the lane number, made once per step by the caller - lane_copy below - and shared with `issue`)
+  auto lane_copy = [&]() { int ln = lane; asm volatile("" : "+v"(ln)); return ln; };
+  auto ahead_issue = [&](uint32_t* entry, uint32_t pp_w, uint32_t r_ptr, const int ln) {
     const uint64_t abase = ((uint64_t)(cont + pp_w)) & ~3ULL;
     const uint32_t rr = r_ptr < a.n_reads ? r_ptr : a.n_reads - 1;
     const uint64_t pbase = (uint64_t)(a.reads_ptr + rr) - 48;
     // two LDS-DMA instructions under their lanes' masks, scalar base + 4 * lane each (lane L lands at entry + 4 L whatever
     // the mask): 12 window dwords, 2 pointers - 14 loads instead of 64, and none of the selects of the one-instruction form
     // (the pointers are loaded by lanes 0, 1 into entry + 12: with one destination the compiler merges the two loads again)
-    int ln = lane;
-    asm volatile("" : "+v"(ln));           // (the two lane masks recomputed per read instead of two scalar register pairs kept across the kernel)
+    // (the two lane masks recomputed per read, from ln, instead of two scalar register pairs kept across the kernel)
     if (ln < 12)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const uint32_t*)abase + lane),
                                        (__attribute__((address_space(3))) void*)entry, 4, 0, 0);
@@ -1310,11 +1342,11 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
   {
     const uint32_t r0 = wave0 < a.n_reads ? wave0 : a.n_reads - 1;
     cur_pp = __builtin_amdgcn_readfirstlane(a.reads_ptr[r0]); cur_pe = __builtin_amdgcn_readfirstlane(a.reads_ptr[r0 + 1]);
-    ahead_issue(ahead0, cur_pp, wave0 + n_waves);
+    ahead_issue(ahead0, cur_pp, wave0 + n_waves, lane_copy());
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     ahead_take(ahead0, cur_pp, cur_hdr, n_pp, n_pe);
-    ahead_issue(ahead1, n_pp, wave0 + 2 * n_waves);
+    ahead_issue(ahead1, n_pp, wave0 + 2 * n_waves, lane_copy());
     ahead_sel = 1;
   }
   // Which instantiations run the software-pipelined road of the loop below: those with k and m as constants - the others are at
@@ -1493,10 +1525,8 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
   };
   // the slots of a round from HBM into the stage area (LDS-DMA; the list of slots sits in the stage area itself: it is consumed
   // before the DMA lands)
-  auto issue = [&](const uint32_t cur, const uint32_t nrun) __attribute__((always_inline)) {
-    uint32_t sidx[MIC_RMAX / 8];
-    int ln = lane;
-    asm volatile("" : "+v"(ln));           // (a lane mask recomputed here instead of a scalar register pair kept across the kernel)
+  auto issue = [&](const uint32_t cur, const uint32_t nrun, const int ln) __attribute__((always_inline)) {
+    uint32_t sidx[MIC_RMAX / 8];          // (ln: a lane mask recomputed here instead of a scalar register pair kept across the kernel)
     __builtin_amdgcn_wave_barrier();
     if (ln < MIC_RMAX) ((uint32_t*)stage)[lane] = cur;
     __builtin_amdgcn_wave_barrier();
@@ -1525,10 +1555,7 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     const int jmax = L.jmax, jmin = L.jmin;
     uint32_t cur = L.cur;
     int remaining = L.remaining;
-    bool again = false;
-    do {
-      if (again) issue(cur, MIC_RMAX);      // (continuation slots: rare; every group of eight under its lanes' mask)
-      again = true;
+    for (;;) {                              // (once; again per continuation slot, whose loads are issued at the loop's end: no flag to test)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
       const bool vl = cur != 0xFFFFFFFFu;
@@ -1538,20 +1565,30 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
       const uint2 kb = *(const uint2*)(q + 4);
       uint32_t e = (ka.x < key) + (ka.y < key) + (ka.z < key) + (ka.w < key) + (kb.x < key) + (kb.y < key);
       const uint32_t mz = q[30];
-      bool more = vl && e < 6;
+      // The lane predicates of the walk are kept as WAVE MASKS (round 11): a compare writes its mask straight into a scalar register
+      // pair, masks are combined by the scalar unit, and a mask goes back into a lane operation as the select of a v_cndmask
+      // (inverse ballot) - a ballot of `a && b` is built as v_cndmask 0 / 1 plus v_cmp instead, twice on the common road until round 10
+      // (the loop's end and the continuation test).  All of this code runs with every lane enabled.
+      const uint64_t m_vl = wballot(vl);
+      uint64_t m_more = m_vl & wballot(e < 6), m_pos = 0;        // (m_pos: set by every pass; 0 for the measuring build that leaves before)
       e = e < 5 ? e : 5;
+#if MIC_X & 8
+      uint32_t ew_pass = 0;
+#endif
       for (;;) {
         uint32_t e3 = e + (e << 1);
         asm volatile("" : "+v"(e3));     // (the compiler would turn 3 e into a 64-bit multiply-add of the LDS address: quarter rate)
-        uint32_t g = q[e], S0 = q[6 + e3], S1 = q[7 + e3], S2 = q[8 + e3], pl = q[24 + e];
+        // (q[e + 1]: the key behind this entry's, read with it - round 11.  For e = 5 it is word 6, no key: never compared, below)
+        uint32_t g = q[e], g1 = q[e + 1], S0 = q[6 + e3], S1 = q[7 + e3], S2 = q[8 + e3], pl = q[24 + e];
         asm volatile("" : "+v"(S2));     // read with the others: the compiler would sink it into the branch below, one more LDS round trip
-        const bool same = more && g == key;
+        const uint64_t m_same = m_more & wballot(g == key);
+        const uint64_t m_next = wballot(g1 == key);
         const uint32_t d0 = G0 ^ S0, d1 = G1 ^ S1, d2 = G2 ^ S2;
         // the whole minimizer, not only its low 32 bits: its nucleotides are the low 32 - 2 ctx bits of word 0 and the top
         // 2 (ctx + m) - 32 bits of word 1 (32-bit operations: the 64-bit form shifts and compares at half rate)
-        const bool mineq = k > 16
-                               ? ((d0 & ((1u << ((32 - 2 * ctx) & 31)) - 1u)) | (d1 >> xsh)) == 0
-                               : (((((uint64_t)d0 << 32) | d1) << (2 * ctx)) >> (64 - 2 * m)) == 0;
+        const uint64_t m_hit = m_same & (k > 16
+                                             ? wballot(((d0 & ((1u << ((32 - 2 * ctx) & 31)) - 1u)) | (d1 >> xsh)) == 0)
+                                             : wballot((((((uint64_t)d0 << 32) | d1) << (2 * ctx)) >> (64 - 2 * m)) == 0));
         const uint32_t dl = d0 >> (32 - 2 * ctx);                                      // left context, nucleotide ctx-1 in the low bits
         const uint32_t dr = k > 16 ? __builtin_amdgcn_alignbit(d1, d2, xsh)
                                         : (uint32_t)((((((uint64_t)d0 << 32) | d1)) << ((2 * k) & 63)) >> 32);   // right context, its first nucleotide on top
@@ -1559,27 +1596,58 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
         const int right = __builtin_clz(dr | (1u << (31 - 2 * ctx))) >> 1;
         const int hi = left < jmax ? left : jmax, lo = ctx - right > jmin ? ctx - right : jmin;
         const uint32_t range = ((2u << (hi & 31)) - 1u) & (~0u << (lo & 31));         // empty when hi < lo
-        const uint32_t hits = (same && mineq) ? (uint32_t)__popc((pl >> 16) & range) : 0u;
-        // the marker of a crowded minimizer (presence mask 0): nothing of this minimizer is in the chains, the lane's walk ends
-        // (kept in `remaining`, as a value no count reaches: a lane mask of its own would cost the loop a scalar register pair)
-#if !(MIC_X & 1)
-        remaining = (same && mineq && (pl >> 16) == 0) ? MIC_R_CROWDED : remaining;
-#endif
+        const uint32_t hits = __builtin_amdgcn_inverse_ballot_w64(m_hit) ? (uint32_t)__popc((pl >> 16) & range) : 0u;
         // The run's hits are tallied ONCE per round: a lane keeps (label, count) of its run; a second entry with ANOTHER
         // label (the same minimizer in two targets' genomes, both contexts matching parts of the run) is tallied on the
         // spot - a wave-uniform branch that is virtually never taken.
+#if MIC_X & 8
+        // measuring build: rounds, rounds with a second pass over the entries, second passes in which a lane finds hits
+        const bool ew_hit = wballot(hits != 0) != 0;
+        if (lane == 0 && ew_pass < 2u) atomicAdd(&g_entry_walk[ew_pass], 1ull);
+        if (lane == 0 && ew_pass == 1u && ew_hit) atomicAdd(&g_entry_walk[2], 1ull);
+        ++ew_pass;
+#endif
         const uint32_t lab_new = (pl & 0xFFFFu) + 1u;
+#if !(MIC_X & 16)
         tally_counts(hits ? lab_new : 0u, hits, acc, n_ent, overflow, total, lane);
+#endif
+#if MIC_X & 32
+        break;
+#endif
+        // the marker of a crowded minimizer (presence mask 0): nothing of this minimizer is in the chains, the lane's walk ends
+        // (kept in `remaining`, as a value no count reaches: a lane mask of its own would cost the loop a scalar register pair)
+#if !(MIC_X & 1)
+        remaining = __builtin_amdgcn_inverse_ballot_w64(m_hit & wballot(pl < 0x10000u)) ? MIC_R_CROWDED : remaining;
+#endif
         remaining -= (int)hits;
-        more = same && remaining > 0 && e < 5;                        // another entry of the same minimizer?
-        e += more ? 1u : 0u;
-        if (!wballot(more)) break;
+        // another entry of the same minimizer?  Only if the NEXT key is ours too (round 11): keys are sorted along the slot and across
+        // the chain, so behind an entry of another key there is none of ours - the pass that only found that out (a run with a
+        // substitution, nothing else stored under its minimizer: one round in ten) is not made.  An unused entry's key is ~0 and its
+        // region words are 0 (mic_build.hip: row_init, s_slot_init): a minimizer whose low word is ~0 walks on over it as before, and
+        // the comparison of the whole minimizer fails there as before.  e = 5: word 6 is no key - `e < 5` masks the comparison.
+        m_pos = wballot(remaining > 0);
+        m_more = m_same & m_pos & wballot(e < 5);
+#if !(MIC_X & 256)
+        m_more &= m_next;
+#endif
+        e += __builtin_amdgcn_inverse_ballot_w64(m_more) ? 1u : 0u;
+        if (!m_more) break;
       }
-      // continuation slot (rare): entries are sorted across the chain, so only if this slot's last key is not above ours
-      const bool nx = vl && remaining > 0 && (mz & MIC_S_NEXT);
+#if MIC_X & 64
+      break;
+#endif
+      // continuation slot (rare): entries are sorted across the chain, so only if this slot's last key is not above ours.  The common
+      // road leaves here on a scalar test: no `cur` to reset, no second ballot.
+      // (`remaining > 0` implies a staged slot: the set-up gives a lane without one no k-mers, and a lane that does not go on to a
+      // continuation slot gives up what it has left, below - so the mask of the lanes with a slot need not live across the walk)
+      const uint64_t m_nx = m_pos & wballot((mz & MIC_S_NEXT) != 0);
+      if (!m_nx) break;
       cur = 0xFFFFFFFFu;
-      if (wballot(nx)) { if (nx && q[5] <= key) cur = q[31]; }
-    } while (wballot(cur != 0xFFFFFFFFu));
+      if (__builtin_amdgcn_inverse_ballot_w64(m_nx) && q[5] <= key) cur = q[31];
+      if (!wballot(cur != 0xFFFFFFFFu)) break;
+      remaining = (cur == 0xFFFFFFFFu && remaining > 0) ? 0 : remaining;
+      issue(cur, MIC_RMAX, lane_copy());    // (continuation slots: rare; every group of eight under its lanes' mask)
+    }
     if (!(MIC_X & 2) && __builtin_expect(wballot(remaining <= MIC_R_CROWDED) != 0, 0)) {
       // Rare (a database with microsatellites, a read that overlaps one): the crowded runs of this round become items of the
       // follow-up's work list - the region as the table orients it and the run's range of minimizer positions; the k-mer with
@@ -1715,7 +1783,7 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
         for (uint32_t rbase = 0; rbase < R; rbase += MIC_RMAX) {
           Round L; uint32_t nrun;
           setup(wd, rbase, R, L, nrun, NoGap{});
-          issue(L.cur, nrun);
+          issue(L.cur, nrun, lane_copy());
           consume(L, acc, n_ent, overflow, total, cg);
         }
       };
@@ -1752,11 +1820,12 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     __builtin_amdgcn_wave_barrier();
     ahead_take(ahead_sel ? ahead1 : ahead0, n_pp, t_hdr, t_pp, t_pe);
     __builtin_amdgcn_wave_barrier();
-    ahead_issue(ahead_sel ? ahead0 : ahead1, t_pp, r + 3 * n_waves);
+    const int ln = lane_copy();                       // (one copy for the two of them: round 11)
+    ahead_issue(ahead_sel ? ahead0 : ahead1, t_pp, r + 3 * n_waves, ln);
     ahead_sel ^= 1;
     cur_pp = n_pp; cur_pe = n_pe; cur_hdr = t_hdr; n_pp = t_pp; n_pe = t_pe;
     p_valid = simple;
-    if (simple) issue(N.cur, n_nrun);
+    if (simple) issue(N.cur, n_nrun, ln);
     r += n_waves;
     return true;
   };

@@ -587,6 +587,14 @@ class MiClarkDB:
         check(self.L.mic_last_query_ms(self.h, C.byref(ms)))
         return float(ms.value)
 
+    def fetch_slots(self, first=0, n=None):
+        """test hook: slots [first, first + n) of a whole super-k-mer table as a (n, 32) uint32 array (include/mi_clark.h)"""
+        if n is None:
+            n = int(self.info()["n_slots"]) - first
+        out = np.empty((n, 32), np.uint32)
+        check(self.L.mic_debug_fetch_slots(self.h, first, n, out.ctypes.data))
+        return out
+
     def last_crowd_stats(self):
         """reads / runs of crowded minimizers the last query_device launch handed to its follow-up kernel"""
         out = (C.c_uint32 * 4)()

@@ -258,6 +258,10 @@ int mic_last_crowd_stats(mic_engine* e, uint32_t out[4]);
 /* test hook: the first `words` 32-bit words of the work area of the last mic_query_device launch (mic_internal.h: header, pending reads,
  * items, pool) and its capacities {pending reads, items, pool words}; MIC_E_STATE when the engine has none.  Synchronous. */
 int mic_debug_fetch_crowd(mic_engine* e, uint32_t* out, size_t words, uint32_t caps[3]);
+/* test hook: slots [first, first + n) of a whole (not parted) super-k-mer table, main slots first, then the continuation slots, as the
+ * kernels read them: 32 words each - sort keys 0..5, three region words per entry 6..23, presence mask << 16 | label 24..29, entries
+ * here | 0x100 if a continuation slot follows in word 30, its index in word 31.  n <= mic_db_info.n_slots - first.  Synchronous. */
+int mic_debug_fetch_slots(mic_engine* e, uint64_t first, uint64_t n, uint32_t* out);
 
 /* ---- device-side ingest: raw FASTA / FASTQ bytes in, result-CSV text out ----------------------------------------
  * The reference does the read indexing (CuCLARK_hh.hh:1339-1534), the 2-bit packing with its N-splitting
