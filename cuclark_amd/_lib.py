@@ -179,6 +179,10 @@ SYMBOLS = [
     ("mic_batch_hitmap", C.c_int, [_VP, _SZ, _VP, _SZ, _VP, _SZ, C.POINTER(C.c_uint64)]),
     ("mic_hitmap_runs_host", C.c_long, [_VP, _VP, _SZ, C.c_uint32, _VP, _SZ]),
     ("mic_hitmap_format", C.c_long, [_VP, _SZ, _VP, _VP, _VP, C.c_uint32, C.c_char_p, _SZ]),
+    ("mic_kraken_start", C.c_int, [_VP, C.POINTER(MicAbundFilter)]),
+    ("mic_kraken_stop", C.c_int, [_VP]),
+    ("mic_ingest_kraken_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("mic_kraken_format", C.c_long, [_VP, _SZ, _VP, _VP, C.c_int, C.c_uint32, C.POINTER(MicAbundFilter), _VP, _VP, _VP, C.c_char_p, _SZ]),
     ("mic_split_start", C.c_int, [_VP, C.POINTER(MicAbundFilter), C.c_int]),
     ("mic_split_stop", C.c_int, [_VP]),
     ("mic_ingest_split_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_VP),

@@ -269,7 +269,8 @@ void Classifier::reset_counts() {
     host_density_.assign(MIC_DENSITY_WORDS, 0);
   }
   if (sketching()) for (mic_engine* e : engines_) check(mic_ksketch_start(e), "k-mer sketches");
-  if (mapping()) for (mic_engine* e : engines_) check(mic_hitmap_start(e), "hit maps");
+  if (kraken()) for (mic_engine* e : engines_) check(mic_kraken_start(e, &opt_.abund_filter), "Kraken format");
+  else if (mapping()) for (mic_engine* e : engines_) check(mic_hitmap_start(e), "hit maps");
   if (!counting()) return;
   for (mic_engine* e : engines_) check(mic_abundance_start(e, &opt_.abund_filter), "abundance counters");
   std::lock_guard<std::mutex> lk(count_mu_);
@@ -488,7 +489,7 @@ void Classifier::run(const std::string& objects, const std::string& results) {
   }
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
   if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
-  if (mapping()) die("--hit-maps does not take list-of-files mode: classify the files one at a time.");
+  if (mapping()) die(std::string(map_option()) + " does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");
@@ -572,7 +573,7 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
   }
   if (!list_mode) { one(f1, f2, results, false); return; }
   if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
-  if (mapping()) die("--hit-maps does not take list-of-files mode: classify the files one at a time.");
+  if (mapping()) die(std::string(map_option()) + " does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
   if (densing()) die("--density does not take list-of-files mode: classify the files with -R and run evaluate_density -F on the result files.");

@@ -41,6 +41,8 @@ struct Options {
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
   std::string classified_out, unclassified_out;              // --classified-out / --unclassified-out <file>: the reads themselves, split (mic_split_*)
   std::string hit_maps;                                      // --hit-maps <file>: per read the runs of k-mer assignments along it (mic_hitmap_*)
+  std::string kraken_out;                                    // --kraken-out <file>: Kraken's per-read file, the hit-map product in another format (mic_kraken_*)
+  std::string kraken_report;                                 // --kraken-report <file>: Kraken's sample report from the abundance counters (kraken_report.hpp)
   uint32_t low_complexity = 0;                               // --mask-low-complexity <level>: DUST level in [1,149], 0 = off (mic_lowc.h)
 };
 
@@ -135,7 +137,8 @@ class Classifier {
   std::atomic<size_t> n_objects_{0};
   // --abundance: every run over the input starts the counters afresh (a run the feeder gives up is repeated from the start)
   // (--kmer-report prints the reads --abundance gives every target: it starts the same counters)
-  bool counting() const { return !opt_.abundance.empty() || sketching(); }
+  // (--kraken-report is formatted from the same counters)
+  bool counting() const { return !opt_.abundance.empty() || !opt_.kraken_report.empty() || sketching(); }
   bool sketching() const { return !opt_.kmer_report.empty(); }
   bool ranking() const { return !opt_.rank_report.empty(); }
   bool densing() const { return !opt_.density.empty(); }
@@ -148,7 +151,13 @@ class Classifier {
   // --hit-maps: the streaming path takes every batch's text from its engine (mic_ingest_hitmap_text); what stays on the host goes
   // through mic_batch_hitmap + mic_hitmap_format in process_segment, into the run's file or - a batch the streaming path handed back -
   // into the sink
-  bool mapping() const { return !opt_.hit_maps.empty(); }
+  // --kraken-out rides the same plumbing (the span in an Item, the file offset per batch, the writer, the sink): another file name,
+  // no header line, and the text comes from mic_ingest_kraken_text / mic_kraken_format.  The command line refuses the two together.
+  bool mapping() const { return !opt_.hit_maps.empty() || kraken(); }
+  bool kraken() const { return !opt_.kraken_out.empty(); }
+  const std::string& map_file() const { return kraken() ? opt_.kraken_out : opt_.hit_maps; }
+  const char* map_header() const { return kraken() ? "" : MIC_HITMAP_HEADER; }
+  const char* map_option() const { return kraken() ? "--kraken-out" : "--hit-maps"; }
   int hitmap_fd_ = -1;                        // run_segments: the file, written in order
   std::string* hitmap_sink_ = nullptr;
   rank::Lineage lineage_;

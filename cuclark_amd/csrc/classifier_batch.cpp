@@ -51,11 +51,11 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
   // --hit-maps: the file with its header line; process_segment appends every segment's text in order
   hitmap_fd_ = -1;
   if (mapping()) {
-    unlink(opt_.hit_maps.c_str());
-    hitmap_fd_ = open(opt_.hit_maps.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
-    const size_t hl = strlen(MIC_HITMAP_HEADER);
-    if (hitmap_fd_ == -1 || write(hitmap_fd_, MIC_HITMAP_HEADER, hl) != (ssize_t)hl) {
-      std::cerr << "Failed to create/open file: " << opt_.hit_maps << std::endl;
+    unlink(map_file().c_str());
+    hitmap_fd_ = open(map_file().c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    const size_t hl = strlen(map_header());      // (--kraken-out: no header line)
+    if (hitmap_fd_ == -1 || write(hitmap_fd_, map_header(), hl) != (ssize_t)hl) {
+      std::cerr << "Failed to create/open file: " << map_file() << std::endl;
       if (hitmap_fd_ != -1) { close(hitmap_fd_); hitmap_fd_ = -1; }
       if (fout) fclose(fout);
       for (int c = 0; c < 2; ++c) if (split_fd_[c] != -1) { close(split_fd_[c]); split_fd_[c] = -1; }
@@ -98,7 +98,7 @@ void Classifier::run_segments(SegmentSource& src, const std::string& results_bas
   if (fout && (fclose(fout) != 0 || write_failed)) { if (err.empty()) err = "cannot write " + csv + " (disk full?)"; }
   for (int c = 0; c < 2; ++c)
     if (split_fd_[c] != -1) { if (close(split_fd_[c]) != 0 && err.empty()) err = "cannot write " + *split_name[c] + " (disk full?)"; split_fd_[c] = -1; }
-  if (hitmap_fd_ != -1) { if (close(hitmap_fd_) != 0 && err.empty()) err = "cannot write " + opt_.hit_maps + " (disk full?)"; hitmap_fd_ = -1; }
+  if (hitmap_fd_ != -1) { if (close(hitmap_fd_) != 0 && err.empty()) err = "cannot write " + map_file() + " (disk full?)"; hitmap_fd_ = -1; }
   release_batches();
   if (!err.empty()) die(err);
   gettimeofday(&t1, nullptr);
@@ -228,11 +228,19 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
           std::vector<std::string> rn(cnt);
           std::vector<const char*> rnp(cnt);
           for (size_t i = 0; i < cnt; ++i) { rn[i].assign((const char*)map + name_s[r0 + i], (size_t)(name_e[r0 + i] - name_s[r0 + i])); rnp[i] = rn[i].c_str(); }
-          const long len = mic_hitmap_format(rnp.data(), cnt, hm_off.data(), hm_words.data(), nm.data(), T, nullptr, 0);
+          // --kraken-out: the same words under the batch's result rows and Length column (mic_kraken.h), no new device call
+          std::vector<uint32_t> kr_norm(kraken() ? cnt : 0);
+          for (size_t i = 0; i < kr_norm.size(); ++i) kr_norm[i] = (uint32_t)(paired ? length[r0 + i] - 1 : length[r0 + i]);
+          const uint32_t* kr_res = L.results + lb * slot_reads_ * MIC_RESULT_WORDS;
+          auto format = [&](char* buf, size_t cap) {
+            return kraken() ? mic_kraken_format(rnp.data(), cnt, kr_res, kr_norm.data(), k, T, &opt_.abund_filter, hm_off.data(), hm_words.data(), nm.data(), buf, cap)
+                            : mic_hitmap_format(rnp.data(), cnt, hm_off.data(), hm_words.data(), nm.data(), T, buf, cap);
+          };
+          const long len = format(nullptr, 0);
           if (len < 0) die("hit maps: the text could not be formatted");
           std::string& ht = hm_out[b];
           ht.resize((size_t)len + 1);
-          if (mic_hitmap_format(rnp.data(), cnt, hm_off.data(), hm_words.data(), nm.data(), T, &ht[0], ht.size()) != len) die("hit maps: the text could not be formatted");
+          if (format(&ht[0], ht.size()) != len) die("hit maps: the text could not be formatted");
           ht.resize((size_t)len);
         }
       } else {
@@ -324,7 +332,7 @@ size_t Classifier::process_segment(const uint8_t* map, size_t nb, bool paired, F
         if (sink_) { if (hitmap_sink_) hitmap_sink_->append(ht); }
         else for (size_t done = 0; done < ht.size() && err.empty();) {
           const ssize_t w = write(hitmap_fd_, ht.data() + done, ht.size() - done);
-          if (w <= 0) { err = "cannot write " + opt_.hit_maps + " (disk full?)"; break; }
+          if (w <= 0) { err = "cannot write " + map_file() + " (disk full?)"; break; }
           done += (size_t)w;
         }
         std::string().swap(ht);

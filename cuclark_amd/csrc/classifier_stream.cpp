@@ -238,11 +238,11 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   int hm_fd = -1;
   uint64_t hm_off = 0;
   if (maps) {
-    unlink(opt_.hit_maps.c_str());
-    hm_fd = open(opt_.hit_maps.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
-    const size_t hl = strlen(MIC_HITMAP_HEADER);
-    if (hm_fd == -1 || pwrite(hm_fd, MIC_HITMAP_HEADER, hl, 0) != (ssize_t)hl) {
-      std::cerr << "Failed to create/open file: " << opt_.hit_maps << std::endl;
+    unlink(map_file().c_str());
+    hm_fd = open(map_file().c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0644);
+    const size_t hl = strlen(map_header());      // (--kraken-out: no header line)
+    if (hm_fd == -1 || pwrite(hm_fd, map_header(), hl, 0) != (ssize_t)hl) {
+      std::cerr << "Failed to create/open file: " << map_file() << std::endl;
       if (hm_fd != -1) close(hm_fd);
       if (out_fd != -1) close(out_fd);
       for (int c = 0; c < 2; ++c) if (split_fd[c] != -1) close(split_fd[c]);
@@ -437,7 +437,8 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
             }
             if (maps) {        // a pointer into the slot's pinned hit-map text, made by the batch's own engine: valid until the writer frees the slot
               uint64_t hb = 0;
-              check(mic_ingest_hitmap_text(engines_[eng], slots[it.slot].slot, &it.hm_text, &hb), "hit-map text");
+              if (kraken()) check(mic_ingest_kraken_text(engines_[eng], slots[it.slot].slot, &it.hm_text, &hb), "Kraken text");
+              else check(mic_ingest_hitmap_text(engines_[eng], slots[it.slot].slot, &it.hm_text, &hb), "hit-map text");
               it.hm_n = (size_t)hb;
             }
           }
@@ -515,7 +516,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
       if (hm_fd != -1) {
         for (size_t hd = 0; hd < it.hm_n;) {
           const ssize_t n = pwrite(hm_fd, it.hm_text + hd, it.hm_n - hd, (off_t)(it.hm_off + hd));
-          if (n <= 0) { fail("Failed to write " + opt_.hit_maps + "."); break; }
+          if (n <= 0) { fail("Failed to write " + map_file() + "."); break; }
           hd += (size_t)n;
         }
       }
@@ -548,7 +549,7 @@ bool Classifier::run_stream(Feeder& feed, const std::string& results_base, bool 
   if (prealloc && ftruncate(out_fd, (off_t)out_off) != 0 && err.empty()) err = "Failed to write the results file.";
   if (out_fd != -1) close(out_fd);
   for (int c = 0; c < 2; ++c) if (split_fd[c] != -1 && close(split_fd[c]) != 0 && err.empty()) err = "Failed to write " + *split_name[c] + ".";
-  if (hm_fd != -1 && close(hm_fd) != 0 && err.empty()) err = "Failed to write " + opt_.hit_maps + ".";
+  if (hm_fd != -1 && close(hm_fd) != 0 && err.empty()) err = "Failed to write " + map_file() + ".";
   const uint64_t tj2 = now_us();
   release_batches();
   const uint64_t tj3 = now_us();

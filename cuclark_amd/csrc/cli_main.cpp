@@ -20,6 +20,7 @@
 #include "classifier.hpp"
 #include "density_report.hpp"
 #include "kmer_report.hpp"
+#include "kraken_report.hpp"
 #include "mic_abund.h"
 
 #define MAXK 32
@@ -71,6 +72,15 @@ static void print_usage(const char* prog) {
                "                     <target>:<k-mers> (0: no target) joined by blanks, | between two stretches of nucleotides (an N, a masked base, the\n"
                "                     two mates of -P) - where the hits fall: a chimera reads A:90 0:30 B:70; -O and -P; not with --db-sharded or a\n"
                "                     list of files; works without -R like --abundance\n";
+  std::cout << "--kraken-out <file>,  also write Kraken's per-read file into <file>, one line per object and no header line:\n"
+               "                     C|U<TAB>name<TAB>label of the 1st assignment (0 on a U line)<TAB>Length<TAB>the hit map as <target>:<k-mers> tokens, |:|\n"
+               "                     between two stretches of nucleotides, 0:0 for an object without k-mers.  C as --classified-out decides it under\n"
+               "                     --min-confidence / --min-gamma; the third column is the target's label, not an LCA; one Length, not a|b, for -P.\n"
+               "                     -O and -P; not with --hit-maps, --db-sharded or a list of files; works without -R like --abundance\n";
+  std::cout << "--kraken-report <file> [--lineage <tsv>] [--kraken-target-rank <rank>],  also write Kraken's sample report of the abundance\n"
+               "                     counts into <file>: %, clade reads, taxon reads, rank code, taxid, indented name.  The tree is the lineage of\n"
+               "                     --rank-report (from <tsv>, else <DB>/../taxonomy; with neither the targets hang under the root); the targets\n"
+               "                     get the code of <rank> (default species); works without -R like --abundance\n";
   std::cout << "--classified-out <file>,  also write the objects that are assigned under --min-confidence / --min-gamma into <file>, as they are in -O\n";
   std::cout << "--unclassified-out <file>,  also write the other objects (no hit, or dropped by the filter) into <file>; either option alone or both;\n"
                "                     one -O input only (not -P, not a list of files); the names are taken as given; work without -R like --abundance\n";
@@ -172,7 +182,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out, hit_maps;
+  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out, hit_maps, kraken_out, kraken_report, kraken_rank = "species";
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -225,6 +235,9 @@ int main(int argc, char** argv) {
     if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
     if (val == "--kmer-report") { need("Please specify the file of the k-mer report!"); kmer_report = argv[i]; if (kmer_report.empty()) { std::cerr << "Please specify the file of the k-mer report!" << std::endl; exit(1); } continue; }
     if (val == "--hit-maps") { need("Please specify the file of the hit maps!"); hit_maps = argv[i]; if (hit_maps.empty()) { std::cerr << "Please specify the file of the hit maps!" << std::endl; exit(1); } continue; }
+    if (val == "--kraken-out") { need("Please specify the file of the Kraken output!"); kraken_out = argv[i]; if (kraken_out.empty()) { std::cerr << "Please specify the file of the Kraken output!" << std::endl; exit(1); } continue; }
+    if (val == "--kraken-report") { need("Please specify the file of the Kraken report!"); kraken_report = argv[i]; if (kraken_report.empty()) { std::cerr << "Please specify the file of the Kraken report!" << std::endl; exit(1); } continue; }
+    if (val == "--kraken-target-rank") { need("Please specify the rank of the targets!"); kraken_rank = argv[i]; continue; }
     if (val == "--rank-report") { need("Please specify the file of the rank report!"); rank_report = argv[i]; continue; }
     if (val == "--lineage") {
       need("Please specify the lineage file!");
@@ -330,7 +343,7 @@ int main(int argc, char** argv) {
     gap = 0;
   }
   if (q_offset && !min_q) { std::cerr << "--quality-offset goes with --min-base-quality <Q>." << std::endl; exit(1); }
-  if (!lineage.empty() && rank_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
+  if (!lineage.empty() && rank_report.empty() && kraken_report.empty()) { std::cerr << "--lineage goes with --rank-report <file>." << std::endl; exit(1); }
   const bool split = !classified_out.empty() || !unclassified_out.empty();
   // two names for one file: the same text, or the same inode when both exist
   auto same_file = [](const std::string& a, const std::string& b) {
@@ -361,6 +374,26 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
+  if (!kraken_out.empty()) {      // refused before any device is touched
+    if (!hit_maps.empty()) { std::cerr << "--kraken-out does not take --hit-maps: the two texts are made in the same buffers, a run writes one of them." << std::endl; exit(1); }
+    if (db_sharded) { std::cerr << "--kraken-out does not take --db-sharded: a map is the labels of one GPU's whole table along the object." << std::endl; exit(1); }
+    for (int io : {i_objects, i_objects2})
+      if (io >= 0 && same_file(kraken_out, argv[io])) { std::cerr << "--kraken-out would overwrite the input: " << kraken_out << std::endl; exit(1); }
+    if (i_results >= 0 && same_file(kraken_out, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kraken-out would overwrite the result CSV: " << kraken_out << std::endl; exit(1); }
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out, &kraken_report})
+      if (same_file(kraken_out, *f)) { std::cerr << "--kraken-out names the file of another output: " << kraken_out << std::endl; exit(1); }
+    if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
+      std::cerr << "--kraken-out does not take list-of-files mode: classify the files one at a time." << std::endl;
+      exit(1);
+    }
+  }
+  if (!kraken_report.empty()) {   // likewise
+    for (int io : {i_objects, i_objects2})
+      if (io >= 0 && same_file(kraken_report, argv[io])) { std::cerr << "--kraken-report would overwrite the input: " << kraken_report << std::endl; exit(1); }
+    if (i_results >= 0 && same_file(kraken_report, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kraken-report would overwrite the result CSV: " << kraken_report << std::endl; exit(1); }
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out, &hit_maps})
+      if (same_file(kraken_report, *f)) { std::cerr << "--kraken-report names the file of another output: " << kraken_report << std::endl; exit(1); }
+  }
   if (split) {      // refused before any device is touched
     if (i_objects2 > 0) { std::cerr << "--classified-out / --unclassified-out do not take paired-end input (-P): one -O file only." << std::endl; exit(1); }
     if (same_file(classified_out, unclassified_out)) { std::cerr << "--classified-out and --unclassified-out name the same file: " << classified_out << std::endl; exit(1); }
@@ -373,11 +406,11 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
-  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || !hit_maps.empty() || split) && i_results < 0 && ext) {
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || !hit_maps.empty() || !kraken_out.empty() || !kraken_report.empty() || split) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && hit_maps.empty() && !split)) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && hit_maps.empty() && kraken_out.empty() && kraken_report.empty() && !split)) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -399,6 +432,7 @@ int main(int argc, char** argv) {
   o.density = density;
   o.kmer_report = kmer_report;
   o.hit_maps = hit_maps;
+  o.kraken_out = kraken_out; o.kraken_report = kraken_report;
   o.classified_out = classified_out; o.unclassified_out = unclassified_out;
   o.min_quality_byte = min_q ? (uint32_t)((q_offset ? q_offset : 33) + min_q) : 0u;
   o.low_complexity = (uint32_t)lowc;
@@ -426,6 +460,17 @@ int main(int argc, char** argv) {
     if (!classified_out.empty()) std::cout << " - Classified objects stored in " << classified_out << std::endl;
     if (!unclassified_out.empty()) std::cout << " - Unclassified objects stored in " << unclassified_out << std::endl;
     if (!hit_maps.empty()) std::cout << " - Hit maps stored in " << hit_maps << std::endl;
+    if (!kraken_out.empty()) std::cout << " - Kraken output stored in " << kraken_out << std::endl;
+    if (!kraken_report.empty()) {   // host formatting over the abundance counters, along --rank-report's lineage when there is one
+      mic::rank::Lineage kl;
+      std::string err;
+      if (!mic::kraken::report_lineage(lineage, o.folder + "../taxonomy", classifier->target_names(), kl, err)) throw std::runtime_error(err);
+      const std::string report = mic::kraken::format_report(classifier->abundance_counts(), kl, kraken_rank);
+      FILE* f = fopen(kraken_report.c_str(), "wb");
+      if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the Kraken report: " + kraken_report);
+      std::cout << " - Kraken report stored in " << kraken_report << std::endl;
+    }
     if (!density.empty()) {
       const std::vector<uint64_t> counts = classifier->density_counts();
       const std::string report = mic::density::format_report(counts.data());

@@ -9,6 +9,9 @@
 // also writes the rank roll-up report (rank_report.hpp; the rule: mic_rollup.h) into <file>: every read's per-target counts - an
 // --extended result CSV carries them, a plain one is refused - are summed along the lineage and the read is counted at the lowest
 // level whose confidence passes -c (gamma as above).  The lineage comes from --lineage, else from <-D>/../taxonomy.
+//   estimate_abundance -F <result.csv> ... --kraken-report <file> [--lineage <tsv> | -D <database directory>] [--kraken-target-rank <name>]
+// also writes Kraken's sample report (kraken_report.hpp) of the same counts into <file>: the cross-check of exe/cuCLARK
+// --kraken-report.  Plain result CSVs will do.  With --lineage the targets are the file's labels; with neither the report is flat.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -23,6 +26,7 @@
 #include "abundance_table.hpp"
 #include "mic_abund.h"
 #include "mic_rollup.h"
+#include "kraken_report.hpp"
 #include "rank_report.hpp"
 #include "result_csv.hpp"
 
@@ -32,7 +36,7 @@ namespace {
   if (msg && *msg) std::cerr << msg << std::endl;
   std::cerr << "Usage: estimate_abundance -F <result.csv> [<result.csv> ...] [-D <database directory>] [-c <min confidence in [0,1]>]"
                " [-g <min gamma in [0,1]>] [-a <min abundance in [0,100]>] [--highconfidence]"
-               " [--rank-report <file> [--lineage <tsv>]]" << std::endl;
+               " [--rank-report <file> [--lineage <tsv>]] [--kraken-report <file> [--lineage <tsv>] [--kraken-target-rank <name>]]" << std::endl;
   exit(1);
 }
 
@@ -40,7 +44,7 @@ namespace {
 
 int main(int argc, char** argv) {
   std::vector<std::string> files;
-  std::string db, rank_report, lineage_file;
+  std::string db, rank_report, lineage_file, kraken_report, kraken_rank = "species";
   mic_abund_filter f = {5, 10, 0, 1};
   uint64_t a_num = 0, a_den = 1;
   for (int i = 1; i < argc; ++i) {
@@ -65,6 +69,10 @@ int main(int argc, char** argv) {
       if (!mic_abund_parse_text(t, 100, &a_num, &a_den)) usage_exit((std::string("The minimum abundance should be a decimal number in [0,100] (at most 9 decimals): ") + t).c_str());
     } else if (v == "--rank-report") {
       rank_report = value("the file of the rank report");
+    } else if (v == "--kraken-report") {
+      kraken_report = value("the file of the Kraken report");
+    } else if (v == "--kraken-target-rank") {
+      kraken_rank = value("the rank of the targets");
     } else if (v == "--lineage") {
       lineage_file = value("the lineage file");
     } else if (v == "--highconfidence") {
@@ -76,7 +84,7 @@ int main(int argc, char** argv) {
     }
   }
   if (files.empty()) usage_exit("Please specify the result file(s) with -F.");
-  if (rank_report.empty() && !lineage_file.empty()) usage_exit("--lineage goes with --rank-report <file>.");
+  if (rank_report.empty() && kraken_report.empty() && !lineage_file.empty()) usage_exit("--lineage goes with --rank-report <file>.");
   if (!rank_report.empty() && lineage_file.empty() && db.empty()) usage_exit("--rank-report needs a lineage: --lineage <tsv>, or -D <database directory> with ../taxonomy next to it.");
   if (!db.empty() && db.back() != '/') db.push_back('/');
   // --rank-report: the lineage over the labels of the first file's header, the counters, the per-read scratch
@@ -168,6 +176,24 @@ int main(int argc, char** argv) {
     const std::string report = mic::rank::format_report(ru_counts, lin);
     FILE* out = fopen(rank_report.c_str(), "wb");
     if (!out || fwrite(report.data(), 1, report.size(), out) != report.size() || fclose(out) != 0) { std::cerr << "Failed to write the rank report: " << rank_report << std::endl; return 1; }
+  }
+  if (!kraken_report.empty()) {
+    // the targets: the lineage file's labels when there is one (it names every target), else the labels that were counted
+    std::vector<std::string> kr_labels = labels;
+    std::string err;
+    if (!lineage_file.empty() && !mic::kraken::lineage_labels(lineage_file, kr_labels, err)) { std::cerr << err << std::endl; return 1; }
+    std::vector<uint64_t> kr_counts(kr_labels.size() + 2, 0);
+    kr_counts[0] = unassigned; kr_counts[1] = filtered;
+    for (const auto& kv : per_label) {
+      const auto at = std::find(kr_labels.begin(), kr_labels.end(), kv.first);
+      if (at == kr_labels.end()) { std::cerr << "--kraken-report: " << kv.first << " is not a label of " << lineage_file << "." << std::endl; return 1; }
+      kr_counts[2 + (size_t)(at - kr_labels.begin())] += kv.second;
+    }
+    mic::rank::Lineage kl;
+    if (!mic::kraken::report_lineage(lineage_file, db.empty() ? std::string() : db + "../taxonomy", kr_labels, kl, err)) { std::cerr << err << std::endl; return 1; }
+    const std::string report = mic::kraken::format_report(kr_counts, kl, kraken_rank);
+    FILE* out = fopen(kraken_report.c_str(), "wb");
+    if (!out || fwrite(report.data(), 1, report.size(), out) != report.size() || fclose(out) != 0) { std::cerr << "Failed to write the Kraken report: " << kraken_report << std::endl; return 1; }
   }
   const std::string table = mic::abund::format_table(counts, labels, &tax, a_num, a_den);
   if (fwrite(table.data(), 1, table.size(), stdout) != table.size() || fflush(stdout) != 0) { std::cerr << "Failed to write the table." << std::endl; return 1; }

@@ -11,6 +11,7 @@
 #include "mi_clark.h"
 #include "mic_internal.h"
 #include "mic_hitmap.h"
+#include "mic_abund.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -68,13 +69,37 @@ int mic_hitmap_start(mic_engine* e) {
   int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
   if (rc) return rc;
   if (t.slots && (t.sharded || t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
-  mic_engine_hitmap(e)->on = true;
+  MicHitmap* hm = mic_engine_hitmap(e);
+  if (hm->on && hm->kraken) return mic_set_error(MIC_E_STATE, "the Kraken format is started on this engine: the two texts share the slots' buffers");
+  hm->on = true;
   return MIC_OK;
 }
 
 int mic_hitmap_stop(mic_engine* e) {
   if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
-  mic_engine_hitmap(e)->on = false;
+  MicHitmap* hm = mic_engine_hitmap(e);
+  if (!hm->kraken) hm->on = false;
+  return MIC_OK;
+}
+
+// the hit-map product in Kraken format (mic_kraken.h): the same engine state with another text behind the same words
+int mic_kraken_start(mic_engine* e, const mic_abund_filter* filter) {
+  if (!e || !filter) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!mic_abund_filter_ok(*filter)) return mic_set_error(MIC_E_INVALID, "a filter threshold is num / 10^d with d <= 9 and num <= 10^d");
+  MicTable t; int sc, ncu, dev, k; uint32_t nt;
+  int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
+  if (rc) return rc;
+  if (t.slots && (t.sharded || t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "the Kraken format on a sharded or parted table: not supported");
+  MicHitmap* hm = mic_engine_hitmap(e);
+  if (hm->on && !hm->kraken) return mic_set_error(MIC_E_STATE, "hit maps are started on this engine: the two texts share the slots' buffers");
+  hm->on = true; hm->kraken = true; hm->filter = *filter;
+  return MIC_OK;
+}
+
+int mic_kraken_stop(mic_engine* e) {
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  MicHitmap* hm = mic_engine_hitmap(e);
+  if (hm->kraken) { hm->on = false; hm->kraken = false; }
   return MIC_OK;
 }
 

@@ -714,3 +714,33 @@ long mic_hitmap_format(const char* const* read_names, size_t n_reads, const uint
   return (long)text.size();
 }
 }  // extern "C"
+
+// ---- the Kraken per-read text: the rule of mic_kraken.h on the CPU (batches that stay on the host, tools/kraken_host_check.cpp) ------
+#include "mic_kraken.h"
+
+namespace {
+struct KrakenAppend { std::string& s; void operator()(char c) { s += c; } };
+struct KrakenTargetName {
+  const char* const* names;
+  void operator()(uint32_t l, KrakenAppend& put) const { put.s += names[l - 1]; }
+};
+}  // namespace
+
+extern "C" long mic_kraken_format(const char* const* read_names, size_t n_reads, const uint32_t* results, const uint32_t* norm, int k,
+                                  uint32_t n_targets, const mic_abund_filter* filter, const uint32_t* offsets, const uint32_t* words,
+                                  const char* const* target_names, char* buf, size_t cap) {
+  if (!filter || !mic_abund_filter_ok(*filter) || n_targets > 65535) return MIC_E_INVALID;
+  if (n_reads && (!read_names || !results || !offsets)) return MIC_E_INVALID;
+  if (n_targets && !target_names) return MIC_E_INVALID;
+  for (uint32_t t = 0; t < n_targets; ++t) if (!target_names[t]) return MIC_E_INVALID;
+  std::string text;
+  KrakenAppend put{text};
+  KrakenTargetName tg{target_names};
+  for (size_t r = 0; r < n_reads; ++r) {
+    if (!read_names[r] || offsets[r + 1] < offsets[r] || (offsets[r + 1] > offsets[r] && !words)) return MIC_E_INVALID;
+    mic_kraken_line(put, (const uint8_t*)read_names[r], (uint32_t)strlen(read_names[r]) < 40 ? strlen(read_names[r]) : 40, results + r * MIC_RESULT_WORDS,
+                    norm ? norm[r] : 0u, k, n_targets, *filter, words ? words + offsets[r] : nullptr, offsets[r + 1] - offsets[r], tg);
+  }
+  if (buf && text.size() < cap) memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
+}

@@ -17,6 +17,7 @@
 #include "mic_qmask.h"
 #include "mic_lowc.h"
 #include "mic_hitmap.h"
+#include "mic_kraken.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -507,6 +508,70 @@ __global__ void __launch_bounds__(256) hitmap_fmt_kernel(HitmapTextArgs a, const
   *p++ = '\n';
 }
 
+// ---- Kraken per-read text (mic_kraken.h: "<C|U>\t<name>\t<taxid>\t<length>\t<map>\n") - the hit-map text's place in the batch and its
+// buffers, another line.  The length kernel is hitmap_len_kernel's shape: one thread per read, 64-bit lengths, the 64-bit exclusive sum.
+// The format kernel is csv_fmt_kernel's shape, not hitmap_fmt_kernel's: a line of a 150-bp read is 60 to 90 bytes, so threads that
+// store their bytes straight to global memory write 60 to 90 bytes apart.  A block's 256 lines are contiguous in the output
+// (line_off[r0] .. line_off[r1]): they are formatted into an LDS stage and the stage is copied out with consecutive lanes on
+// consecutive addresses - dwords over the aligned middle, bytes at the two ends; the stage is shifted by the output's misalignment, so
+// that a dword of the stage is a dword of the output.  A block whose text does not fit the stage (long reads, many runs) stores
+// directly.  Both kernels count and write through mic_kraken_line: they cannot disagree about a line's length.
+struct KrakenTextArgs {
+  HitmapTextArgs h;
+  const uint32_t* results; const uint32_t* length; uint32_t norm_sub; int k;
+  mic_abund_filter filter;
+};
+
+struct KrakenCount { unsigned long long n; __device__ __forceinline__ void operator()(char) { ++n; } };
+template <typename P> struct KrakenStore { P p; __device__ __forceinline__ void operator()(char c) { *p++ = c; } };
+struct KrakenTarget {
+  const char* tnames; const uint32_t* tname_off;
+  template <typename Put> __device__ __forceinline__ void operator()(uint32_t l, Put& put) const {
+    const uint32_t a = tname_off[l - 1], b = tname_off[l];
+    for (uint32_t i = a; i < b; ++i) put(tnames[i]);
+  }
+};
+template <typename Put> __device__ __forceinline__ void kraken_line_of(const KrakenTextArgs& a, uint32_t r, Put& put) {
+  const uint32_t w0 = a.h.offsets[r], w1 = a.h.offsets[r + 1];
+  KrakenTarget tg{a.h.tnames, a.h.tname_off};
+  mic_kraken_line(put, a.h.raw + a.h.name_s[r], a.h.name_len[r], a.results + (size_t)r * 8, a.length[r] - a.norm_sub, a.k, a.h.n_targets, a.filter,
+                  a.h.words + w0, w1 - w0, tg);
+}
+
+__global__ void __launch_bounds__(256) kraken_len_kernel(KrakenTextArgs a, unsigned long long* __restrict__ line_len) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r > a.h.n_reads) return;
+  if (r == a.h.n_reads) { line_len[r] = 0; return; }
+  KrakenCount cnt{0};
+  kraken_line_of(a, r, cnt);
+  line_len[r] = cnt.n;
+}
+
+// 24 KiB, csv_fmt_kernel's size: 256 lines of up to 96 bytes, which holds the 60 to 90 bytes of a 150-bp read's line; six blocks
+// (24 of a CU's 32 waves) fit the 160 KiB of LDS, and a larger stage would buy longer lines with resident waves
+#define KRAKEN_LDS 24576
+__global__ void __launch_bounds__(256) kraken_fmt_kernel(KrakenTextArgs a, const unsigned long long* __restrict__ line_off, char* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) char s_buf[KRAKEN_LDS];
+  const uint32_t r0 = blockIdx.x * 256, r = r0 + threadIdx.x;
+  const uint32_t r1 = r0 + 256 < a.h.n_reads ? r0 + 256 : a.h.n_reads;
+  const unsigned long long b0 = line_off[r0], b1 = line_off[r1];
+  const uint32_t sh = (uint32_t)((uintptr_t)(out + b0) & 3u);           // stage byte sh + i is output byte b0 + i
+  const bool staged = b1 - b0 <= (unsigned long long)(KRAKEN_LDS - 3);
+  if (r < a.h.n_reads) {
+    if (staged) { KrakenStore<char*> put{s_buf + sh + (uint32_t)(line_off[r] - b0)}; kraken_line_of(a, r, put); }
+    else { KrakenStore<char*> put{out + line_off[r]}; kraken_line_of(a, r, put); }
+  }
+  if (staged) {
+    __syncthreads();
+    const uint32_t end = sh + (uint32_t)(b1 - b0), t = threadIdx.x;
+    char* g = out + b0 - sh;                                              // 4-byte aligned; bytes [sh, end) are this block's
+    const uint32_t body = sh ? 4u : 0u, e4 = end & ~3u;
+    if (sh && t >= sh && t < 4u && t < end) g[t] = s_buf[t];
+    for (uint32_t i = body / 4u + t; i < e4 / 4u; i += 256) ((uint32_t*)g)[i] = ((const uint32_t*)s_buf)[i];
+    if (e4 >= body && e4 + t < end) g[e4 + t] = s_buf[e4 + t];
+  }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 // ---- a pair of FASTQ texts resident on the device (the inflated mates of -P a.fq.gz b.fq.gz): line index, checks, merge --------------
 // The reference merges a pair line by line into ">id\nseq1Nseq2\n" (file.cc:205-268); the command line's loaders do that on the
@@ -671,7 +736,7 @@ struct Slot {
   uint32_t* d_hm_words = nullptr; size_t hm_words_cap = 0;
   char* d_hm_text = nullptr; char* h_hm_text = nullptr; size_t hm_text_cap = 0;
   uint64_t* h_hm_tot = nullptr;
-  bool hm_valid = false;
+  bool hm_valid = false, hm_kraken = false;      // hm_kraken: the text is the Kraken format's (mic_kraken_start)
   // table-sharded batches (mic_ingest_classify_group): what this slot keeps on every engine of its group, the owner included
   struct Peer {
     mic_engine* eng = nullptr; int device = 0;
@@ -1312,6 +1377,7 @@ struct BatchCtx {
   uint32_t n_reads = 0, nb = 0, gr = 0; int paired = 0, fasta = 0; uint32_t lpr = 4;   // gr: blocks of 256 over n_reads + 1 items; lpr: lines per FASTQ record
   // e's base-quality threshold (pack_kernel<true, *>) and low-complexity level (lowc_kernel, pack_kernel<*, true>), 0: none; the modes; e's split setting
   uint32_t c0 = 0, lc = 0; bool no_csv = false, roll = false, resident = false, hitmaps = false; MicSplit sp;
+  MicHitmap hm;                                                         // e's hit-map setting: the text's format, the Kraken format's filter
   hipStream_t st = nullptr, up = nullptr, down = nullptr;               // the slot's stream; e's upload and download streams
 };
 
@@ -1349,7 +1415,7 @@ int begin_batch(mic_engine* const* group, size_t n_group, size_t owner, size_t s
   MIC_TRY(hipSetDevice(b.dev));
   Slot& s = *(b.s = &g->slots[slot_id]);
   s.ru_valid = false; s.split_valid = false; s.hm_valid = false;
-  b.hitmaps = mic_engine_hitmap(e)->on;
+  b.hm = *mic_engine_hitmap(e); b.hitmaps = b.hm.on;
   if (b.hitmaps && (b.t.sharded || b.t.parted)) return mic_set_error(MIC_E_UNSUPPORTED, "hit maps on a sharded or parted table: not supported");
   memset(out, 0, sizeof(*out));
   b.resident = (flags & MIC_INGEST_RESIDENT) != 0;      // the text is in the slot's device buffer already (mic_pairs_merge_to_slot: merged pairs)
@@ -1542,20 +1608,27 @@ int hitmap_product(BatchCtx& b) {
   HitmapTextArgs ha;
   ha.raw = s.d_raw; ha.name_s = s.rec.name_s; ha.name_len = s.rec.name_len; ha.offsets = s.d_hm_off; ha.words = s.d_hm_words;
   ha.tnames = g->d_tnames; ha.tname_off = g->d_tname_off; ha.n_targets = g->n_targets; ha.n_reads = n_reads;
-  hitmap_len_kernel<<<b.gr, 256, 0, st>>>(ha, s.d_hm_len);
+  KrakenTextArgs ka;                          // the Kraken format (mic_kraken_start): the same place, buffers and scan, another pair of text kernels
+  if (b.hm.kraken) {
+    ka.h = ha; ka.results = s.d_results; ka.length = s.rec.length; ka.norm_sub = b.paired ? 1u : 0u; ka.k = b.k; ka.filter = b.hm.filter;
+    kraken_len_kernel<<<b.gr, 256, 0, st>>>(ka, s.d_hm_len);
+  } else {
+    hitmap_len_kernel<<<b.gr, 256, 0, st>>>(ha, s.d_hm_len);
+  }
   size_t tb = s.hm_tmp_bytes;
   MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_hm_tmp, tb, s.d_hm_len, s.d_hm_loff, (int)(n_reads + 1), st));
   MIC_TRY(hipMemcpyAsync(s.h_hm_tot + 1, s.d_hm_loff + n_reads, 8, hipMemcpyDeviceToHost, st));
   MIC_TRY(wait_stream(s, st));
   const size_t n_text = (size_t)s.h_hm_tot[1];
   if ((rc = ensure_hitmap_buffers(g, s, 0, n_text))) return rc;
-  hitmap_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ha, s.d_hm_loff, s.d_hm_text);
+  if (b.hm.kraken) kraken_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ka, s.d_hm_loff, s.d_hm_text);
+  else hitmap_fmt_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(ha, s.d_hm_loff, s.d_hm_text);
   MIC_TRY(hipGetLastError());
   MIC_TRY(hipEventRecord(s.ev_k, st));
   MIC_TRY(hipStreamWaitEvent(b.down, s.ev_k, 0));
   MIC_TRY(hipMemcpyAsync(s.h_hm_text, s.d_hm_text, n_text, hipMemcpyDeviceToHost, b.down));
   if ((rc = wait_down_without_csv(b))) return rc;
-  s.hm_valid = true;
+  s.hm_valid = true; s.hm_kraken = b.hm.kraken;
   return MIC_OK;
 }
 
@@ -1658,7 +1731,21 @@ int mic_ingest_hitmap_text(mic_engine* e, size_t slot_id, const uint8_t** text, 
   if (!e || !text || !bytes) return mic_set_error(MIC_E_INVALID, "null argument");
   Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
   const Slot& s = g->slots[slot_id];
+  if (mic_engine_hitmap(e)->kraken || (s.hm_valid && s.hm_kraken))
+    return mic_set_error(MIC_E_STATE, "the Kraken format is on: the slot's text is mic_ingest_kraken_text's");
   if (!s.hm_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no hit-map text (mic_hitmap_start, MIC_INGEST_OK)");
+  *text = (const uint8_t*)s.h_hm_text; *bytes = s.h_hm_tot[1];
+  return MIC_OK;
+}
+
+int mic_ingest_kraken_text(mic_engine* e, size_t slot_id, const uint8_t** text, uint64_t* bytes) {
+  if (!e || !text || !bytes) return mic_set_error(MIC_E_INVALID, "null argument");
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
+  const Slot& s = g->slots[slot_id];
+  const MicHitmap& hm = *mic_engine_hitmap(e);
+  if ((hm.on && !hm.kraken) || (s.hm_valid && !s.hm_kraken))
+    return mic_set_error(MIC_E_STATE, "the hit-map format is on: the slot's text is mic_ingest_hitmap_text's");
+  if (!s.hm_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no Kraken text (mic_kraken_start, MIC_INGEST_OK)");
   *text = (const uint8_t*)s.h_hm_text; *bytes = s.h_hm_tot[1];
   return MIC_OK;
 }

@@ -257,8 +257,12 @@ hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const
 
 // ---- hit maps (mic_hitmap.hip; the kernel: mic_kernels.hip; the text kernels: mic_ingest.hip; the rule: mic_hitmap.h) ----------------
 // An engine's setting while mic_hitmap_start is in force: every ingest batch it owns that returns MIC_INGEST_OK gets its map and text.
+// kraken: the text is Kraken's per-read line (mic_kraken_start; the rule: mic_kraken.h) instead of the hit-map line - the same two probe
+// passes, the same slot buffers, another pair of text kernels; a run has one text or the other.
 struct MicHitmap {
   bool on = false;
+  bool kraken = false;
+  mic_abund_filter filter = {5, 10, 0, 1};
 };
 // one pass of hitmap_kernel over reads [0, n_reads): fill == false: out = n_reads + 1 word counts (item n_reads = 0), offsets unused;
 // fill == true: out = the words, offsets = the exclusive sum of the counts (n_reads + 1).  n_cu caps the grid.

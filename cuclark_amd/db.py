@@ -523,6 +523,23 @@ class MiClarkDB:
         check(self.L.mic_ingest_hitmap_text(self.h, slot, C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value) if n.value else b""
 
+    # -- Kraken's per-read text (mic_kraken_*): the hit-map product in another format (csrc/mic_kraken.h); filt as for abundance_start
+    def kraken_start(self, filt=None):
+        """From now on every ingest batch of this engine that returns MIC_INGEST_OK gets its Kraken per-read text.  MicError
+        (MIC_E_STATE) while hit maps are started: a run has one text or the other."""
+        from . import host
+        f = filt if filt is not None else host.abund_filter()
+        check(self.L.mic_kraken_start(self.h, C.byref(f)))
+
+    def kraken_stop(self):
+        check(self.L.mic_kraken_stop(self.h))
+
+    def ingest_kraken_text(self, slot):
+        """bytes: the Kraken per-read text of the slot's last batch; MicError (MIC_E_STATE) when it left none."""
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        check(self.L.mic_ingest_kraken_text(self.h, slot, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
     def batch_hitmap(self, batch, n_reads):
         """(offsets u32[n_reads + 1], words u32) of a batch of the batch API (after its wait; n_reads as given to readyBatch): sized
         with one call, filled with a second."""

@@ -280,6 +280,30 @@ def hitmap_format(read_names, offsets, words, target_names):
     return buf.raw[:ln]
 
 
+def kraken_format(read_names, results, norm, k, offsets, words, target_names, filt=None):
+    """mic_kraken_format: the text of exe/cuCLARK --kraken-out (csrc/mic_kraken.h), as bytes.  read_names, offsets, words and
+    target_names as for hitmap_format; results u32[n, 8]; norm: the CSV's Length column per read, or None; filt as for abundance_host."""
+    L = _lib.load()
+    enc = lambda s: s.encode() if isinstance(s, str) else bytes(s)
+    n, T = len(read_names), len(target_names)
+    f = filt if filt is not None else abund_filter()
+    res = np.ascontiguousarray(results, np.uint32).reshape(-1, 8)
+    nm = None if norm is None else np.ascontiguousarray(norm, np.uint32).reshape(-1)
+    off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+    wd = np.ascontiguousarray(words, np.uint32).reshape(-1)
+    assert res.shape[0] == n and (nm is None or nm.size == n) and off.size == n + 1 and (n == 0 or int(off[-1]) <= wd.size)
+    rn = (C.c_char_p * max(n, 1))(*[enc(s) for s in read_names])
+    tn = (C.c_char_p * max(T, 1))(*[enc(s) for s in target_names])
+    args = (rn, n, res.ctypes.data if n else None, None if nm is None else nm.ctypes.data, int(k), T, C.byref(f), off.ctypes.data,
+            wd.ctypes.data if wd.size else None, tn)
+    ln = L.mic_kraken_format(*args, None, 0)
+    if ln < 0:
+        raise ValueError(f"mic_kraken_format: invalid argument ({ln})")
+    buf = C.create_string_buffer(ln + 1)
+    assert L.mic_kraken_format(*args, buf, ln + 1) == ln
+    return buf.raw[:ln]
+
+
 def rollup_check(n_targets, group_of):
     """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
     1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""

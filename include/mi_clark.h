@@ -704,6 +704,30 @@ long mic_hitmap_runs_host(const uint32_t* labels, const uint32_t* part_nk, size_
 long mic_hitmap_format(const char* const* read_names, size_t n_reads, const uint32_t* offsets, const uint32_t* words,
                        const char* const* target_names, uint32_t n_targets, char* buf, size_t cap);
 
+/* ---- Kraken's per-read file, made on the device (csrc/mic_kraken.h: the rule, shared by host and device) ----
+ * One line per read in input order, no header line: "<C|U>\t<name>\t<taxid>\t<length>\t<map>\n".  C iff the read is classified under
+ * the filter (the predicate of mic_split_start), <name> as the hit-map text prints it, <taxid> the name of target idxBest - 1 on a C
+ * line (the target's label, not an LCA) and 0 on a U line, <length> the CSV's Length column (one number, merged pairs: minus one),
+ * <map> the hit-map words as "<target>:<len>" tokens joined by single blanks, every separator word "|:|", an empty map "0:0".
+ * mic_kraken_start / _stop   puts the engine's hit-map product (mic_hitmap_start) into this format: the same two probe passes and the
+ *                        same slot buffers, another pair of text kernels.  A run has one text or the other: started while hit maps
+ *                        are started (or mic_hitmap_start while this is) returns MIC_E_STATE.  Refused like hit maps
+ *                        (MIC_E_UNSUPPORTED): a sharded or parted table, a group of more than one engine.  MIC_E_INVALID for a
+ *                        filter mic_abundance_start would refuse.  A stop call of the format that is not on does nothing.
+ * mic_ingest_kraken_text the text of the slot's last batch, as mic_ingest_hitmap_text gives the hit-map text.  MIC_E_STATE while the
+ *                        hit-map format is on and when the last batch left none (handed back, or not started);
+ *                        mic_ingest_hitmap_text returns MIC_E_STATE while this format is on.
+ * mic_kraken_format      the text of n_reads reads on the host (no device needed): names as for mic_hitmap_format, result rows, norm
+ *                        (the Length column per read; NULL: 0), the maps of mic_batch_hitmap / mic_hitmap_device.  Returns the
+ *                        length (written with a terminator when it fits cap; buf may be NULL to ask) or MIC_E_INVALID (a null
+ *                        argument, descending offsets, a filter that is not valid). */
+int mic_kraken_start(mic_engine* e, const mic_abund_filter* filter);
+int mic_kraken_stop(mic_engine* e);
+int mic_ingest_kraken_text(mic_engine* e, size_t slot, const uint8_t** text, uint64_t* bytes);
+long mic_kraken_format(const char* const* read_names, size_t n_reads, const uint32_t* results, const uint32_t* norm, int k, uint32_t n_targets,
+                       const mic_abund_filter* filter, const uint32_t* offsets, const uint32_t* words, const char* const* target_names,
+                       char* buf, size_t cap);
+
 /* "%g" of (double)num / den for 0 < num <= den, by the integer-only formatter the device CSV kernel uses
  * (csrc/mic_fmt.h); writes at most 14 characters and a terminator, returns the length. */
 int mic_format_ratio_g(uint32_t num, uint32_t den, char* out16);

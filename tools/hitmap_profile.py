@@ -1,11 +1,13 @@
 """The workload behind DESIGN.md 4.11's device-time figures, to be run under a kernel trace:
 
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/hitmap_profile.py [--off]
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/hitmap_profile.py [--off | --kraken | --both]
 
 mic_ingest_classify of 2 M synthetic 150-bp reads as four-line FASTQ, twice, in 38 batches of 106 k reads, T = 4096, a 128 M-nucleotide
 database (4.10's setup), with the hit maps started (--off: not started), so that one trace holds query_kernel_r, pack_kernel, the two
 instantiations of hitmap_kernel, hitmap_len_kernel and hitmap_fmt_kernel on the same batches.  Prints the number of batches, the bytes
-of hit-map text and the tokens in it."""
+of hit-map text and the tokens in it.  --kraken: the product in Kraken format (kraken_len_kernel / kraken_fmt_kernel in
+place of the two hit-map text kernels); --both: the passes with hit maps, then the same passes in Kraken format, so that one trace
+holds both pairs of text kernels on the same batches."""
 import argparse
 import ctypes as C
 import os
@@ -16,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 N_READS, BATCH, T, K = 2_000_000, 106_000, 4096, 31
 
 
-def main(off):
+def main(off, formats=("hitmap",)):
     import torch
     from cuclark_amd import MiClarkDB, _lib
     L = _lib.load()
@@ -37,27 +39,32 @@ def main(off):
     text = d_text[: N_READS * rb].cpu().numpy().tobytes()
     with MiClarkDB(K, T) as e:
         e.read_device(d_sizes.data_ptr(), htsize, d_keys.data_ptr(), 8, d_labels.data_ptr())
-        if not off:
-            e.hitmap_start()                # (in front of the slots: their hit-map buffers come with them)
-        e.ingest_alloc(1, BATCH * rb + 4096, [f"L{i}" for i in range(T)])
-        ok = back = n_bytes = n_tokens = n_seps = 0
-        for _ in range(2):                  # two passes over the 19 batches: 38 launches of every kernel
-            for r0 in range(0, N_READS, BATCH):
-                out = e.ingest_classify(0, text[r0 * rb:min(N_READS, r0 + BATCH) * rb])
-                ok += out["status"] == 0
-                back += out["status"] != 0
-                if not off and out["status"] == 0:
-                    hm = e.ingest_hitmap_text(0)
-                    n_bytes += len(hm)
-                    n_tokens += hm.count(b":")
-                    n_seps += hm.count(b"|")
-        print(f"ingest: {ok} batches, {back} handed back, {rb} bytes per record, hit maps {'off' if off else 'on'}")
-        if not off:
-            print(f"hit maps: {n_bytes} bytes of text, {n_tokens} runs, {n_seps} separators, {n_tokens / max(1, 2 * N_READS):.2f} runs per read")
+        for fmt in formats:
+            if not off:                     # (in front of the slots: their hit-map buffers come with them)
+                e.kraken_start() if fmt == "kraken" else e.hitmap_start()
+            e.ingest_alloc(1, BATCH * rb + 4096, [f"L{i}" for i in range(T)])
+            ok = back = n_bytes = n_tokens = n_seps = 0
+            for _ in range(2):                  # two passes over the 19 batches: 38 launches of every kernel
+                for r0 in range(0, N_READS, BATCH):
+                    out = e.ingest_classify(0, text[r0 * rb:min(N_READS, r0 + BATCH) * rb])
+                    ok += out["status"] == 0
+                    back += out["status"] != 0
+                    if not off and out["status"] == 0:
+                        hm = e.ingest_kraken_text(0) if fmt == "kraken" else e.ingest_hitmap_text(0)
+                        n_bytes += len(hm)
+                        n_tokens += hm.count(b":")
+                        n_seps += hm.count(b"|")
+            print(f"ingest: {ok} batches, {back} handed back, {rb} bytes per record, {fmt} text {'off' if off else 'on'}")
+            if not off:
+                print(f"{fmt}: {n_bytes} bytes of text, {n_tokens} runs, {n_seps} separators, {n_tokens / max(1, 2 * N_READS):.2f} runs per read")
+                e.kraken_stop() if fmt == "kraken" else e.hitmap_stop()
+            e.ingest_free()
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--off", action="store_true")
+    ap.add_argument("--kraken", action="store_true")
+    ap.add_argument("--both", action="store_true")
     a = ap.parse_args()
-    main(a.off)
+    main(a.off, ("hitmap", "kraken") if a.both else ("kraken",) if a.kraken else ("hitmap",))

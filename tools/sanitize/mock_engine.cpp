@@ -229,6 +229,10 @@ int mic_hitmap_start(mic_engine*) { return MIC_OK; }
 int mic_hitmap_stop(mic_engine*) { return MIC_OK; }
 int mic_ingest_hitmap_text(mic_engine*, size_t, const uint8_t**, uint64_t*) { return MIC_E_STATE; }
 int mic_batch_hitmap(mic_engine*, size_t, uint32_t*, size_t, uint32_t*, size_t, uint64_t*) { return MIC_E_STATE; }
+// the Kraken format of the same product: likewise (mic_kraken_format is mic_host.cpp's)
+int mic_kraken_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
+int mic_kraken_stop(mic_engine*) { return MIC_OK; }
+int mic_ingest_kraken_text(mic_engine*, size_t, const uint8_t**, uint64_t*) { return MIC_E_STATE; }
 }  // extern "C"
 
 namespace {
