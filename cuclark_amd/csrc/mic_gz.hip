@@ -1,7 +1,7 @@
 // mic_gz.hip - gzip inflated ON THE DEVICE: the two-stage scheme of csrc/pgz.hpp (pugz / rapidgzip) with one decode
 // unit per deflate block - thousands of wavefronts - instead of sixteen threads.  BASELINE config 5 names gzip FASTQ; the
 // reference's scripts gunzip to a temporary file first (classify_metagenome.sh:116-142).  The command line's path for compressed
-// FASTQ on one engine: the text stays on the device, where the pair merge and the ingest kernels read it (mic_ingest.hip:
+// FASTQ on one engine: the text stays on the device, where the pair merge and the ingest kernels read it (mic_text.hip:
 // mic_pairs_*, mic_text_*).  316 MB of FASTQ out of 59 MB of gzip in 12 ms (pgz.hpp on the 16 allowed CPUs: 3 GB/s); a
 // block-gzip file (BGZF) of the same text, a wavefront per member, in 14-15 ms.  tests/test_gz_device.py, tools/gz_device_timing.py.
 //

@@ -1,7 +1,7 @@
 // mic_ingest.hip — device-side ingest: raw FASTA / FASTQ bytes in, result-CSV text out (include/mi_clark.h, mic_ingest_*).
 //
 // Moves onto the GPU what the reference does on the host around queryBatch, for well-formed input:
-//   read indexing            CuCLARK_hh.hh:1339-1534   -> line_count / line_start / record kernels
+//   read indexing            CuCLARK_hh.hh:1339-1534   -> line_count / line_start (mic_text.hip) / record kernels
 //   2-bit packing, N-split   CuCLARK_hh.hh:1616-1716   -> pack_kernel  (same container format, same part rules)
 //   result CSV lines         CuCLARK_hh.hh:1951-2139   -> csv_len / csv_fmt kernels ("%g" exact, mic_fmt.h)
 // The host only moves bytes: file -> pinned buffer -> (H2D) ... (D2H) -> pinned buffer -> file.
@@ -11,6 +11,8 @@
 // mic_pack_reads, mic_csv_line): an empty read name (the reference's name scan then crosses the line end), a FASTA
 // record without a sequence line, a truncated FASTQ record, a sequence longer than MIC_MAX_PART bytes, more lines or
 // reads than the slot was sized for, a read that needs the dense fallback of the query kernel.
+// This file is the ingest SLOTS.  The line indexer, and the index of whole texts resident on the device (mic_text_*, mic_pairs_*: the
+// inflated input of -O x.fq.gz / -P a.fq.gz b.fq.gz), are mic_text.hip, which reaches a slot through mic_ingest_slot_text.
 #include "mi_clark.h"
 #include "mic_internal.h"
 #include "mic_fmt.h"
@@ -36,65 +38,6 @@
 namespace {
 
 enum { H_NLINES = 0, H_NREADS = 1, H_STATUS = 2, H_CSV_BYTES = 3, H_FLAGGED = 4, H_NEWLINES = 5, H_CONT = 6, H_WORDS = 8 };
-
-#define ING_TILE 4096          // bytes per block of the line kernels (256 threads x 16 B)
-
-__device__ __forceinline__ uint32_t newline_mask(uint32_t x) {       // 0x80 in every byte of x that is '\n'
-  const uint32_t y = x ^ 0x0A0A0A0Au;
-  return ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
-}
-
-// newline flags of the 16 bytes at byte offset `pos` (16-byte aligned): bit i = byte i is '\n' and lies below nb
-// (from: bytes below it are not the text's - the front of an aligned-down buffer, mic_text_index_front_device)
-__device__ __forceinline__ uint32_t tile_flags(const uint8_t* __restrict__ raw, uint32_t pos, uint32_t nb, uint32_t from = 0) {
-  if (pos >= nb || pos + 16 <= from) return 0;
-  const uint4 v = *(const uint4*)(raw + pos);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  uint32_t f = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t m = newline_mask(w[i]);     // bits 7, 15, 23, 31
-    f |= (((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u)) << (4 * i);
-  }
-  const uint32_t left = nb - pos;
-  if (left < 16) f &= (1u << left) - 1u;
-  if (pos < from) f &= ~((1u << (from - pos)) - 1u);
-  return f;
-}
-
-__global__ void __launch_bounds__(256) line_count_kernel(const uint8_t* __restrict__ raw, uint32_t nb, uint32_t* __restrict__ tile_cnt, uint32_t from = 0) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t pos = blockIdx.x * ING_TILE + threadIdx.x * 16;
-  uint32_t c = __popc(tile_flags(raw, pos, nb, from));
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// line_start[L] = offset of the first byte of line L (line 0 starts at 0; a '\n' at p starts the next line at p + 1)
-__global__ void __launch_bounds__(256) line_start_kernel(const uint8_t* __restrict__ raw, uint32_t nb, const uint32_t* __restrict__ tile_off,
-                                                         uint32_t* __restrict__ line_start, uint32_t cap, uint32_t from = 0) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t pos = blockIdx.x * ING_TILE + threadIdx.x * 16;
-  uint32_t f = tile_flags(raw, pos, nb, from);
-  const uint32_t c = __popc(f);
-  uint32_t inc = c;                               // inclusive scan inside the wave
-  const int lane = threadIdx.x & 63;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) s_w[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  uint32_t base = tile_off[blockIdx.x];
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += s_w[w];
-  uint32_t rank = base + inc - c;                 // newlines before this thread's bytes
-  if (blockIdx.x == 0 && threadIdx.x == 0) line_start[0] = from;
-  while (f) {
-    const int b = __ffs((int)f) - 1;
-    f &= f - 1;
-    ++rank;
-    if (rank < cap) line_start[rank] = pos + (uint32_t)b + 1u;
-  }
-}
 
 // one thread: number of lines (an unterminated last line counts and gets a virtual line end at nb), FASTQ record count
 __global__ void lines_finish_kernel(const uint8_t* __restrict__ raw, uint32_t nb, const uint32_t* __restrict__ tile_off, uint32_t n_tiles,
@@ -573,134 +516,8 @@ __global__ void __launch_bounds__(256) kraken_fmt_kernel(KrakenTextArgs a, const
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-// ---- a pair of FASTQ texts resident on the device (the inflated mates of -P a.fq.gz b.fq.gz): line index, checks, merge --------------
-// The reference merges a pair line by line into ">id\nseq1Nseq2\n" (file.cc:205-268); the command line's loaders do that on the
-// host for plain files.  Text that was inflated ON the device (mic_gz.hip) is merged here instead, record ranges straight into an
-// ingest slot's device buffer, so that the text never crosses the link.  Whatever the line arithmetic does not cover (line
-// counts that differ or are no multiple of four, a header without '@', ids that differ or are empty) is reported, and the
-// caller goes back to the host reader, which treats such files the way the reference does, messages included.
-enum { PS_LINES = MIC_PAIRS_LINES, PS_HEADER = MIC_PAIRS_HEADER, PS_ID = MIC_PAIRS_ID, PS_BIG = MIC_PAIRS_BIG };
-
-__device__ __forceinline__ bool pair_sep(uint8_t c) { return c == ' ' || c == '/' || c == '\t' || c == '@'; }     // file.cc:224
-// the id inside a header line [p, p + n): behind leading separators, up to the next one
-__device__ __forceinline__ void pair_id(const uint8_t* __restrict__ p, uint32_t n, uint32_t& a, uint32_t& len) {
-  a = 0;
-  while (a < n && pair_sep(p[a])) ++a;
-  uint32_t b = a;
-  while (b < n && !pair_sep(p[b])) ++b;
-  len = b - a;
-}
-
-struct PairText { const uint8_t* t; const uint32_t* ls; uint32_t nb; };
-// line L of a text without its '\n' (an unterminated last line has its virtual line end at nb: line_start = nb + 1)
-__device__ __forceinline__ void pair_line(const PairText& x, uint64_t L, const uint8_t*& p, uint32_t& n) {
-  const uint32_t a = x.ls[L], b = x.ls[L + 1];
-  p = x.t + a; n = b - 1u - a;
-}
-
-// one thread per record: checks, and the length of the merged record
-__global__ void __launch_bounds__(256) pair_len_kernel(PairText A, PairText B, uint64_t n_rec, unsigned long long* __restrict__ mlen,
-                                                       uint32_t* __restrict__ status) {
-  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r > n_rec) return;
-  if (r == n_rec) { mlen[r] = 0; return; }
-  const uint8_t *p, *q; uint32_t n, m;
-  pair_line(A, 4 * r, p, n); pair_line(B, 4 * r, q, m);
-  uint32_t bad = 0, ia = 0, la = 0, ib = 0, lb = 0;
-  if (n == 0 || m == 0 || p[0] != '@' || q[0] != '@') bad |= PS_HEADER;
-  else {
-    pair_id(p, n, ia, la); pair_id(q, m, ib, lb);
-    if (la == 0 || la != lb) bad |= PS_ID;
-    else for (uint32_t i = 0; i < la; ++i) if (p[ia + i] != q[ib + i]) { bad |= PS_ID; break; }
-  }
-  const uint32_t s1 = A.ls[4 * r + 2] - 1u - A.ls[4 * r + 1], s2 = B.ls[4 * r + 2] - 1u - B.ls[4 * r + 1];
-  mlen[r] = (unsigned long long)la + 2u + s1 + 1u + s2 + 1u;
-  if (bad) atomicOr(status, bad);
-}
-
-__global__ void __launch_bounds__(256) pair_sample_kernel(const unsigned long long* __restrict__ off, uint64_t n_rec, uint32_t stride,
-                                                          uint64_t n_samples, unsigned long long* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_samples) return;
-  const uint64_t r = i * stride;
-  out[i] = off[r < n_rec ? r : n_rec];
-}
-
-// a single FASTQ text: out[i] = byte offset of record min(i * stride, n_rec) (line 4 r; behind the last record: the end of the text)
-__global__ void __launch_bounds__(256) text_sample_kernel(const uint32_t* __restrict__ ls, uint32_t nb, uint64_t n_rec, uint32_t stride,
-                                                          uint64_t n_samples, unsigned long long* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_samples) return;
-  const uint64_t r = i * stride < n_rec ? i * stride : n_rec;
-  const uint32_t o = ls[4 * r];
-  out[i] = o < nb ? o : nb;
-}
-
-// FASTA: flag[L] = line L starts a record ('>' in its first column, CuCLARK_hh.hh:1369-1389); flag[n_lines] = 0 for the scan's total
-__global__ void __launch_bounds__(256) text_fasta_flag_kernel(const uint8_t* __restrict__ raw, uint32_t nb, const uint32_t* __restrict__ ls,
-                                                              uint64_t n_lines, uint32_t* __restrict__ flag) {
-  const uint64_t L = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (L > n_lines) return;
-  uint32_t f = 0;
-  if (L < n_lines) { const uint32_t p = ls[L]; f = p < nb && raw[p] == '>'; }
-  flag[L] = f;
-}
-// out[r / stride] = byte offset of record r for every stride-th record; the entries behind the last one: the end of the text
-__global__ void __launch_bounds__(256) text_fasta_sample_kernel(const uint32_t* __restrict__ ls, const uint32_t* __restrict__ flag,
-                                                                const uint32_t* __restrict__ rec_of_line, uint64_t n_lines, uint32_t stride,
-                                                                unsigned long long* __restrict__ out) {
-  const uint64_t L = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (L >= n_lines || !flag[L]) return;
-  const uint32_t r = rec_of_line[L];
-  if (r % stride == 0) out[r / stride] = ls[L];
-}
-
 // (the device code of this file is loaded when its first kernel is launched: mic_ingest_alloc does that, not the first batch)
 __global__ void ingest_warm_kernel(uint32_t* p) { if (p && threadIdx.x == 1000) *p = 0; }
-
-// what the host wants to know about a text once its line ends are counted, gathered for ONE small copy (a copy into pageable host
-// memory costs about a millisecond whatever its size): out[0] = line ends, out[1] = last byte, out[2] = first byte
-__global__ void text_facts_kernel(const uint8_t* __restrict__ raw, uint32_t nb, const uint32_t* __restrict__ tile_off, uint32_t n_tiles,
-                                  uint32_t* __restrict__ out, uint32_t from = 0) {
-  out[0] = tile_off[n_tiles]; out[1] = raw[nb - 1]; out[2] = raw[from]; out[3] = 0;
-}
-
-// one wavefront per record: ">id\n" seq1 "N" seq2 "\n" at off[r] - off[r0]
-// QUAL (a threshold byte c0 is set on the engine): each mate's sequence is copied with 'N' in place of every base its own quality
-// line (line 4r + 3 of its text) masks (mic_qmask.h); the lengths are those of pair_len_kernel either way
-template <bool QUAL>
-__global__ void __launch_bounds__(256) pair_merge_kernel(PairText A, PairText B, uint64_t r0, uint64_t r1, const unsigned long long* __restrict__ off,
-                                                         uint8_t* __restrict__ dst, uint32_t c0) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t r = r0 + (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= r1) return;
-  uint8_t* o = dst + (off[r] - off[r0]);
-  const uint8_t *p, *q; uint32_t n, m;
-  pair_line(A, 4 * r, p, n);
-  uint32_t ia, la;
-  pair_id(p, n, ia, la);
-  if (lane == 0) o[0] = '>';
-  for (uint32_t i = lane; i < la; i += 64) o[1 + i] = p[ia + i];
-  if (lane == 0) o[1 + la] = '\n';
-  o += la + 2;
-  const uint8_t* u = nullptr; uint32_t un = 0;       // QUAL: the mate's quality line
-  pair_line(A, 4 * r + 1, p, n);
-  if (QUAL) pair_line(A, 4 * r + 3, u, un);
-  for (uint32_t i = lane; i < n; i += 64) o[i] = (QUAL && mic_qmask_masked(u, un, i, c0)) ? (uint8_t)'N' : p[i];
-  if (lane == 0) o[n] = 'N';
-  o += n + 1;
-  pair_line(B, 4 * r + 1, q, m);
-  if (QUAL) pair_line(B, 4 * r + 3, u, un);
-  for (uint32_t i = lane; i < m; i += 64) o[i] = (QUAL && mic_qmask_masked(u, un, i, c0)) ? (uint8_t)'N' : q[i];
-  if (lane == 0) o[m] = '\n';
-}
-
-void launch_pair_merge(const PairText& A, const PairText& B, uint64_t r0, uint64_t r1, const unsigned long long* off, uint8_t* dst, uint32_t c0,
-                       hipStream_t st) {
-  const unsigned blocks = (unsigned)((r1 - r0 + 3) / 4);
-  if (c0) pair_merge_kernel<true><<<blocks, 256, 0, st>>>(A, B, r0, r1, off, dst, c0);
-  else pair_merge_kernel<false><<<blocks, 256, 0, st>>>(A, B, r0, r1, off, dst, 0u);
-}
 
 struct Slot {
   // pinned host
@@ -1022,8 +839,6 @@ int ensure_hitmap_buffers(Ingest* g, Slot& s, size_t words, size_t text) {
   return MIC_OK;
 }
 
-double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec / 1e9; }
-
 // ---- table-sharded batches: the slot's buffers on the engines of its group, and the exchange ------------------------------
 const uint32_t kGroupRowWords = 16;      // 15 (target, count) pairs per partial row = the reference's MAXHITS rows (parameters.hh:44)
 
@@ -1265,28 +1080,6 @@ void group_harvest(Ingest* g, Slot& s, uint32_t n) {
 
 }  // namespace
 
-struct mic_text {
-  const uint8_t* t = nullptr; uint32_t nb = 0;
-  void* d_scratch = nullptr; void* d_block = nullptr;
-  uint32_t* d_ls = nullptr;
-  uint64_t n_rec = 0;
-  uint32_t stride = 64;
-  std::vector<unsigned long long> samples;      // byte offset of record i * stride, then the size of the text
-  int device = 0;
-  bool fasta = false;
-};
-
-struct mic_pairs {
-  PairText t[2];
-  void* d_scratch = nullptr; void* d_block = nullptr;     // the two device allocations everything below is carved from
-  uint32_t* d_ls[2] = {nullptr, nullptr};
-  unsigned long long* d_off = nullptr;          // off[r] = bytes of merged text in front of record r (n_rec + 1 entries)
-  uint64_t n_rec = 0;
-  uint32_t stride = 64;
-  std::vector<unsigned long long> samples;      // off[i * stride] for the host's batch arithmetic, then off[n_rec]
-  int device = 0;
-};
-
 extern "C" {
 
 int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char* const* target_names, uint32_t n_targets,
@@ -1301,8 +1094,8 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
   mic_ingest_free(e);
   Ingest* g = new Ingest();
   g->eng = e; g->device = dev;
-  g->max_bytes = (max_bytes + ING_TILE - 1) / ING_TILE * ING_TILE;
-  g->max_tiles = g->max_bytes / ING_TILE;
+  g->max_bytes = (max_bytes + MIC_LINE_TILE - 1) / MIC_LINE_TILE * MIC_LINE_TILE;
+  g->max_tiles = g->max_bytes / MIC_LINE_TILE;
   g->max_lines = g->max_bytes / 16 + 64;          // fewer than 16 bytes per line on average: host path
   g->max_reads = g->max_bytes / 32 + 16;          // fewer than 32 bytes per record on average: host path
   // sum of the per-read reservations of record_kernel: nbytes / 8 + 2 (nbytes / (k + 1) + 1) + 8 containers per read
@@ -1322,13 +1115,13 @@ int mic_ingest_alloc(mic_engine* e, size_t n_slots, size_t max_bytes, const char
     }
     MIC_TRY(hipMalloc(&g->d_tnames, names.size() + 16));
     ingest_warm_kernel<<<1, 64>>>((uint32_t*)g->d_tnames);       // (loads this file's device code now, not with the first batch)
+    (void)mic_text_warm(nullptr);                                // (and the line kernels', which live in mic_text.hip)
     MIC_TRY(hipMalloc(&g->d_tname_off, off.size() * 4));
     if (!names.empty()) MIC_TRY(hipMemcpy(g->d_tnames, names.data(), names.size(), hipMemcpyHostToDevice));
     MIC_TRY(hipMemcpy(g->d_tname_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
   }
   g->slots.resize(n_slots);
-  size_t tmp1 = 0, tmp2 = 0, tmp3 = 0;
-  hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(g->max_tiles + 1));
+  size_t tmp1 = mic_line_scan_bytes(g->max_tiles), tmp2 = 0, tmp3 = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(g->max_lines + 1));
   hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(g->max_reads + 1));
   const size_t tmp = std::max(tmp1, std::max(tmp2, tmp3)) + 256;
@@ -1431,18 +1224,15 @@ int begin_batch(mic_engine* const* group, size_t n_group, size_t owner, size_t s
 // upload stream, the CSV comes back on its download stream (mic_engine.hip: one stream per direction keeps both directions busy)
 int index_records(BatchCtx& b, mic_ingest_result* out) {
   Ingest* g = b.g; Slot& s = *b.s; const hipStream_t st = b.st;
-  const uint32_t nb = b.nb, n_tiles = (nb + ING_TILE - 1) / ING_TILE, lpr = b.lpr; const int fasta = b.fasta;
+  const uint32_t nb = b.nb, n_tiles = mic_line_tiles(nb), lpr = b.lpr; const int fasta = b.fasta;
   if (!b.resident) {
     MIC_TRY(hipMemcpyAsync(s.d_raw, s.h_raw, nb, hipMemcpyHostToDevice, b.up));
     MIC_TRY(hipEventRecord(s.ev_up, b.up));
     MIC_TRY(hipStreamWaitEvent(st, s.ev_up, 0));
   }
   MIC_TRY(hipMemsetAsync(s.d_hdr, 0, H_WORDS * 4, st));
-  line_count_kernel<<<n_tiles, 256, 0, st>>>(s.d_raw, nb, s.d_tile);
-  MIC_TRY(hipMemsetAsync(s.d_tile + n_tiles, 0, 4, st));
-  size_t tb = s.tmp_bytes;
-  MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_tile, s.d_tile_off, (int)(n_tiles + 1), st));
-  line_start_kernel<<<n_tiles, 256, 0, st>>>(s.d_raw, nb, s.d_tile_off, s.d_line_start, (uint32_t)g->max_lines);
+  MIC_TRY(mic_line_ends(s.d_raw, nb, 0, s.d_tile, s.d_tile_off, s.d_tmp, s.tmp_bytes, st));
+  MIC_TRY(mic_line_starts(s.d_raw, nb, 0, s.d_tile_off, s.d_line_start, (uint32_t)g->max_lines, st));
   lines_finish_kernel<<<1, 1, 0, st>>>(s.d_raw, nb, s.d_tile_off, n_tiles, s.d_line_start, (uint32_t)g->max_lines, fasta, lpr, (uint32_t)g->max_reads, s.d_hdr);
   if (fasta) {
     // a line is at least one byte long, so there are at most nb of them: flags and their scan cover lines 0 .. n_scan - 1
@@ -1450,7 +1240,7 @@ int index_records(BatchCtx& b, mic_ingest_result* out) {
     const uint32_t n_scan = (uint32_t)std::min<size_t>(g->max_lines, (size_t)nb + 2);
     const uint32_t gl = (n_scan + 255) / 256;
     fasta_flag_kernel<<<gl, 256, 0, st>>>(s.d_raw, nb, s.d_line_start, s.d_hdr, (uint32_t)g->max_lines, n_scan, s.d_flag);
-    tb = s.tmp_bytes;
+    size_t tb = s.tmp_bytes;
     MIC_TRY(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, tb, s.d_flag, s.d_rec_of_line, (int)n_scan, st));
     fasta_scatter_kernel<<<gl, 256, 0, st>>>(s.d_flag, s.d_rec_of_line, (uint32_t)g->max_lines, (uint32_t)g->max_reads, s.d_hdr_line, s.d_hdr);
   }
@@ -1647,6 +1437,12 @@ int csv_to_host(BatchCtx& b, uint32_t csv_bytes) {
 
 }  // namespace
 
+int mic_ingest_slot_text(mic_engine* e, size_t slot_id, MicSlotText* out) {
+  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
+  *out = {g->slots[slot_id].d_raw, g->slots[slot_id].stream, g->max_bytes, g->device};
+  return MIC_OK;
+}
+
 extern "C" {
 
 int mic_ingest_classify_group(mic_engine* const* group, size_t n_group, size_t owner, size_t slot_id, size_t n_bytes, int flags,
@@ -1747,346 +1543,6 @@ int mic_ingest_kraken_text(mic_engine* e, size_t slot_id, const uint8_t** text, 
     return mic_set_error(MIC_E_STATE, "the hit-map format is on: the slot's text is mic_ingest_hitmap_text's");
   if (!s.hm_valid) return mic_set_error(MIC_E_STATE, "the slot's last batch left no Kraken text (mic_kraken_start, MIC_INGEST_OK)");
   *text = (const uint8_t*)s.h_hm_text; *bytes = s.h_hm_tot[1];
-  return MIC_OK;
-}
-
-// ---- paired-end texts on the device -------------------------------------------------------------------------------------
-int mic_pairs_free(mic_engine* e, mic_pairs* p) {
-  (void)e;
-  if (!p) return MIC_OK;
-  hipSetDevice(p->device);
-  if (p->d_scratch) hipFree(p->d_scratch);
-  if (p->d_block) hipFree(p->d_block);
-  delete p;
-  return MIC_OK;
-}
-
-// Two device allocations and no hipFree on the way (each costs about a millisecond and a device-wide wait): a scratch block for the
-// line counts of both texts, then - once the numbers of lines are known - one block for everything that depends on them.
-int mic_pairs_index_device(mic_engine* e, const void* d_text1, size_t n1, const void* d_text2, size_t n2, mic_pairs** out,
-                           uint64_t* n_records, uint32_t* status) {
-  if (!e || !d_text1 || !d_text2 || !out || !n_records || !status) return mic_set_error(MIC_E_INVALID, "null argument");
-  *out = nullptr; *n_records = 0; *status = 0;
-  if (n1 == 0 || n2 == 0 || n1 >= 0xFFFFFF00ull || n2 >= 0xFFFFFF00ull) { *status = PS_BIG; return MIC_OK; }   // 32-bit line starts
-  MicTable t; int sc, ncu, dev, k; uint32_t nt;
-  int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
-  if (rc) return rc;
-  if (hipSetDevice(dev) != hipSuccess) return mic_set_error(MIC_E_HIP, "hipSetDevice failed");
-  mic_pairs* p = new mic_pairs;
-  p->device = dev;
-  const uint8_t* raw[2] = {(const uint8_t*)d_text1, (const uint8_t*)d_text2};
-  const uint32_t nb[2] = {(uint32_t)n1, (uint32_t)n2};
-  const uint32_t n_tiles[2] = {(nb[0] + ING_TILE - 1) / ING_TILE, (nb[1] + ING_TILE - 1) / ING_TILE};
-  uint64_t n_lines[2] = {0, 0};
-  uint32_t nl[2] = {0, 0}; uint8_t last[2] = {0, 0};
-  hipStream_t st = nullptr;
-  uint32_t* d_tile[2]; uint32_t* d_tile_off[2]; void* d_tmp = nullptr; uint32_t* d_facts = nullptr;
-  uint32_t facts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  size_t tmp_bytes = 0, tmp2 = 0;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  static const bool timing = getenv("MIC_GZ_TIMING") != nullptr;
-  double tl = timing ? now_s() : 0;
-  auto lap = [&](const char* what) { if (!timing) return; const double t = now_s(); fprintf(stderr, "[pairs] %s: %.3f ms\n", what, (t - tl) * 1e3); tl = t; };
-  { hipStream_t up_, down_; mic_engine_copy_streams(e, &up_, &down_); st = up_; }      // (a stream of its own would cost 2 ms to create)
-  {
-    size_t t0 = 0, t1 = 0;
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, t0, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[0] + 1), st));
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles[1] + 1), st));
-    tmp_bytes = std::max(t0, t1);
-    const size_t a0 = up(((size_t)n_tiles[0] + 1) * 4), a1 = up(((size_t)n_tiles[1] + 1) * 4);
-    MIC_TRY_DONE(hipMalloc(&p->d_scratch, 2 * a0 + 2 * a1 + 256 + up(tmp_bytes + 16)));
-    char* q = (char*)p->d_scratch;
-    d_tile[0] = (uint32_t*)q; q += a0; d_tile_off[0] = (uint32_t*)q; q += a0;
-    d_tile[1] = (uint32_t*)q; q += a1; d_tile_off[1] = (uint32_t*)q; q += a1;
-    d_facts = (uint32_t*)q; q += 256;
-    d_tmp = q;
-  }
-  lap("scratch allocated");
-  for (int i = 0; i < 2; ++i) {
-    line_count_kernel<<<n_tiles[i], 256, 0, st>>>(raw[i], nb[i], d_tile[i]);
-    MIC_TRY_DONE(hipMemsetAsync(d_tile[i] + n_tiles[i], 0, 4, st));
-    size_t tb = tmp_bytes;
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile[i], d_tile_off[i], (int)(n_tiles[i] + 1), st));
-    text_facts_kernel<<<1, 1, 0, st>>>(raw[i], nb[i], d_tile_off[i], n_tiles[i], d_facts + 4 * i);
-  }
-  MIC_TRY_DONE(hipGetLastError());
-  MIC_TRY_DONE(hipMemcpyAsync(facts, d_facts, 32, hipMemcpyDeviceToHost, st));
-  MIC_TRY_DONE(hipStreamSynchronize(st));
-  for (int i = 0; i < 2; ++i) { nl[i] = facts[4 * i]; last[i] = (uint8_t)facts[4 * i + 1]; }
-  lap("lines counted");
-  for (int i = 0; i < 2; ++i) n_lines[i] = (uint64_t)nl[i] + (last[i] != '\n' ? 1 : 0);
-  if (n_lines[0] != n_lines[1] || n_lines[0] % 4 != 0 || n_lines[0] == 0) { *status = PS_LINES; goto done; }
-  {
-    const uint64_t n_rec = n_lines[0] / 4;
-    p->n_rec = n_rec;
-    const uint64_t n_samples = n_rec / p->stride + 2;
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(n_rec + 1), st));
-    const size_t b_ls = up((n_lines[0] + 2) * 4), b_off = up((n_rec + 1) * 8), b_smp = up(n_samples * 8);
-    MIC_TRY_DONE(hipMalloc(&p->d_block, 2 * b_ls + 2 * b_off + b_smp + 256 + up(tmp2 + 16)));
-    char* q = (char*)p->d_block;
-    p->d_ls[0] = (uint32_t*)q; q += b_ls; p->d_ls[1] = (uint32_t*)q; q += b_ls;
-    p->d_off = (unsigned long long*)q; q += b_off;
-    unsigned long long* d_mlen = (unsigned long long*)q; q += b_off;
-    unsigned long long* d_samples = (unsigned long long*)q; q += b_smp;
-    uint32_t* d_status = (uint32_t*)q; q += 256;
-    void* d_tmp2 = q;
-    lap("index block allocated");
-    for (int i = 0; i < 2; ++i) {
-      line_start_kernel<<<n_tiles[i], 256, 0, st>>>(raw[i], nb[i], d_tile_off[i], p->d_ls[i], (uint32_t)std::min<uint64_t>(n_lines[i] + 2, 0xFFFFFFFFull));
-      MIC_TRY_DONE(hipGetLastError());
-      if (last[i] != '\n') {                   // the virtual line end of an unterminated last line (lines_finish_kernel's convention)
-        nl[i] = nb[i] + 1;                     // (nl[] is done with; the source of an asynchronous copy has to outlive it)
-        MIC_TRY_DONE(hipMemcpyAsync(p->d_ls[i] + n_lines[i], &nl[i], 4, hipMemcpyHostToDevice, st));
-      }
-      p->t[i].t = raw[i]; p->t[i].ls = p->d_ls[i]; p->t[i].nb = nb[i];
-    }
-    MIC_TRY_DONE(hipMemsetAsync(d_status, 0, 4, st));
-    pair_len_kernel<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(p->t[0], p->t[1], n_rec, d_mlen, d_status);
-    MIC_TRY_DONE(hipGetLastError());
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_mlen, p->d_off, (int)(n_rec + 1), st));
-    p->samples.resize(n_samples);
-    pair_sample_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(p->d_off, n_rec, p->stride, n_samples, d_samples);
-    MIC_TRY_DONE(hipGetLastError());
-    MIC_TRY_DONE(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
-    MIC_TRY_DONE(hipMemcpyAsync(status, d_status, 4, hipMemcpyDeviceToHost, st));
-    MIC_TRY_DONE(hipStreamSynchronize(st));
-    lap("line starts, pair checks, offsets, samples");
-  }
-done:
-  if (st) hipStreamSynchronize(st);
-  if (rc != MIC_OK || *status) { mic_pairs_free(e, p); return rc; }
-  *out = p; *n_records = p->n_rec;
-  return MIC_OK;
-}
-
-// bytes of merged text in front of record r, for r a multiple of the stride or r == n_records
-static bool pairs_offset(const mic_pairs* p, uint64_t r, unsigned long long& off) {
-  if (r == p->n_rec) { off = p->samples.back() ; return true; }
-  if (r > p->n_rec || r % p->stride) return false;
-  off = p->samples[r / p->stride];
-  return true;
-}
-
-int mic_pairs_offsets(const mic_pairs* p, const uint64_t** samples, size_t* n_samples, uint32_t* stride) {
-  if (!p || !samples || !n_samples || !stride) return mic_set_error(MIC_E_INVALID, "null argument");
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
-  *samples = (const uint64_t*)p->samples.data(); *n_samples = p->samples.size(); *stride = p->stride;
-  return MIC_OK;
-}
-
-int mic_pairs_merge_to_slot(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r1, size_t slot_id, size_t* n_bytes) {
-  if (!e || !p || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
-  unsigned long long o0, o1;
-  if (r0 >= r1 || !pairs_offset(p, r0, o0) || !pairs_offset(p, r1, o1))
-    return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
-  if (o1 - o0 > g->max_bytes) return mic_set_error(MIC_E_INVALID, "merged text of %llu bytes does not fit the slot (%zu)", o1 - o0, g->max_bytes);
-  // the kernel runs on the SLOT's device and stream; when the texts live on another device (several engines, one inflated input)
-  // it reads them through peer access
-  if (g->device != p->device && !mic_peer_enable(g->device, p->device))
-    return mic_set_error(MIC_E_UNSUPPORTED, "device %d has no peer access to device %d, where the inflated text lives", g->device, p->device);
-  MIC_TRY(hipSetDevice(g->device));
-  Slot& s = g->slots[slot_id];
-  launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, s.d_raw, *mic_engine_min_quality(e), s.stream);
-  MIC_TRY(hipGetLastError());
-  *n_bytes = (size_t)(o1 - o0);
-  return MIC_OK;
-}
-
-int mic_pairs_text(mic_engine* e, mic_pairs* p, uint64_t r0, uint64_t r1, void* host_dst, size_t cap, size_t* n_bytes) {
-  if (!e || !p || !host_dst || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  unsigned long long o0, o1;
-  if (r0 >= r1 || !pairs_offset(p, r0, o0) || !pairs_offset(p, r1, o1))
-    return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
-  *n_bytes = (size_t)(o1 - o0);
-  if (*n_bytes > cap) return mic_set_error(MIC_E_INVALID, "merged text of %zu bytes does not fit the buffer (%zu)", *n_bytes, cap);
-  MIC_TRY(hipSetDevice(p->device));
-  uint8_t* d = nullptr;
-  MIC_TRY(hipMalloc(&d, *n_bytes + 16));
-  launch_pair_merge(p->t[0], p->t[1], r0, r1, p->d_off, d, *mic_engine_min_quality(e), 0);
-  hipError_t he = hipGetLastError();
-  if (he == hipSuccess) he = hipMemcpy(host_dst, d, *n_bytes, hipMemcpyDeviceToHost);
-  hipFree(d);
-  MIC_TRY(he);
-  return MIC_OK;
-}
-
-// ---- one FASTQ text on the device (the inflated file of -O reads.fq.gz): where its records start ---------------------------
-int mic_text_free(mic_engine* e, mic_text* p) {
-  (void)e;
-  if (!p) return MIC_OK;
-  hipSetDevice(p->device);
-  if (p->d_scratch) hipFree(p->d_scratch);
-  if (p->d_block) hipFree(p->d_block);
-  delete p;
-  return MIC_OK;
-}
-
-// partial: the text is the front of a longer one (a stripe of a member still being inflated, mic_gz_stream_next) - FASTQ only, the
-// whole records of it are indexed (lines that end in '\n', four to a record), *n_used = where the first record that is not whole
-// starts; no whole record yet: MIC_OK, *out = nullptr, *n_used = 0
-static int text_index(mic_engine* e, const void* d_text, size_t n, bool partial, mic_text** out, uint64_t* n_records, uint64_t* n_used, uint32_t* status);
-
-int mic_text_index_device(mic_engine* e, const void* d_text, size_t n, mic_text** out, uint64_t* n_records, uint32_t* status) {
-  uint64_t used = 0;
-  return text_index(e, d_text, n, false, out, n_records, &used, status);
-}
-
-int mic_text_index_front_device(mic_engine* e, const void* d_text, size_t n, mic_text** out, uint64_t* n_records, uint64_t* n_used, uint32_t* status) {
-  if (!n_used) return mic_set_error(MIC_E_INVALID, "null argument");
-  return text_index(e, d_text, n, true, out, n_records, n_used, status);
-}
-
-static int text_index(mic_engine* e, const void* d_text, size_t n, bool partial, mic_text** out, uint64_t* n_records, uint64_t* n_used, uint32_t* status) {
-  if (!e || !d_text || !out || !n_records || !status) return mic_set_error(MIC_E_INVALID, "null argument");
-  *out = nullptr; *n_records = 0; *status = 0; *n_used = 0;
-  if (n == 0 || n >= 0xFFFFFF00ull) { *status = PS_BIG; return MIC_OK; }
-  MicTable t; int sc, ncu, dev, k; uint32_t nt;
-  int rc = mic_engine_table(e, &t, &sc, &ncu, &dev, &k, &nt);
-  if (rc) return rc;
-  if (hipSetDevice(dev) != hipSuccess) return mic_set_error(MIC_E_HIP, "hipSetDevice failed");
-  mic_text* p = new mic_text;
-  // the kernels read 16 aligned bytes a thread: the text counts from the 4-KiB boundary in front of it, `from` bytes are not its own
-  const uint32_t from = (uint32_t)((uintptr_t)d_text & 4095u);
-  if (n + from >= 0xFFFFFF00ull) { delete p; *status = PS_BIG; return MIC_OK; }
-  p->device = dev; p->t = (const uint8_t*)d_text - from; p->nb = (uint32_t)(n + from);
-  const uint8_t* raw = p->t;
-  const uint32_t nb = p->nb, n_tiles = (nb + ING_TILE - 1) / ING_TILE;
-  uint32_t nl = 0; uint8_t first = 0, last = 0;
-  uint64_t n_lines = 0;
-  hipStream_t st = nullptr;
-  uint32_t* d_tile = nullptr; uint32_t* d_tile_off = nullptr; void* d_tmp = nullptr; uint32_t* d_facts = nullptr;
-  uint32_t facts[4] = {0, 0, 0, 0};
-  size_t tmp_bytes = 0;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  { hipStream_t up_, down_; mic_engine_copy_streams(e, &up_, &down_); st = up_; }      // (a stream of its own would cost 2 ms to create)
-  MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_tiles + 1), st));
-  {
-    const size_t a0 = up(((size_t)n_tiles + 1) * 4);
-    MIC_TRY_DONE(hipMalloc(&p->d_scratch, 2 * a0 + 256 + up(tmp_bytes + 16)));
-    char* q = (char*)p->d_scratch;
-    d_tile = (uint32_t*)q; q += a0; d_tile_off = (uint32_t*)q; q += a0; d_facts = (uint32_t*)q; q += 256; d_tmp = q;
-  }
-  line_count_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile, from);
-  MIC_TRY_DONE(hipMemsetAsync(d_tile + n_tiles, 0, 4, st));
-  {
-    size_t tb = tmp_bytes;
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_tile, d_tile_off, (int)(n_tiles + 1), st));
-  }
-  text_facts_kernel<<<1, 1, 0, st>>>(raw, nb, d_tile_off, n_tiles, d_facts, from);
-  MIC_TRY_DONE(hipGetLastError());
-  MIC_TRY_DONE(hipMemcpyAsync(facts, d_facts, 16, hipMemcpyDeviceToHost, st));
-  MIC_TRY_DONE(hipStreamSynchronize(st));
-  nl = facts[0]; last = (uint8_t)facts[1]; first = (uint8_t)facts[2];
-  n_lines = (uint64_t)nl + (last != '\n' ? 1 : 0);
-  if (partial) {
-    if (first != '@') { *status = PS_HEADER; goto done; }
-    n_lines = (uint64_t)nl / 4 * 4;              // whole records of whole lines; what follows is the next call's
-    last = '\n';
-    if (n_lines == 0) { mic_text_free(e, p); return MIC_OK; }
-  }
-  if (first == '>') {
-    // FASTA: a record is a '>' line and what follows it up to the next one (sequences over several lines)
-    p->fasta = true;
-    const size_t b_ls = up((n_lines + 2) * 4), b_fl = up((n_lines + 1) * 4);
-    size_t tmp2 = 0;
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n_lines + 1), st));
-    if (n_lines >= 0x7FFFFFF0ull) { *status = PS_BIG; goto done; }
-    // (the samples are sized by the lines - there are no more records than lines - and cut down once the count is known)
-    const size_t b_smp = up((n_lines / p->stride + 2) * 8);
-    MIC_TRY_DONE(hipMalloc(&p->d_block, b_ls + 2 * b_fl + b_smp + up(tmp2 + 16)));
-    p->d_ls = (uint32_t*)p->d_block;
-    uint32_t* d_flag = (uint32_t*)((char*)p->d_block + b_ls);
-    uint32_t* d_rec = (uint32_t*)((char*)p->d_block + b_ls + b_fl);
-    unsigned long long* d_samples = (unsigned long long*)((char*)p->d_block + b_ls + 2 * b_fl);
-    void* d_tmp2 = (char*)p->d_block + b_ls + 2 * b_fl + b_smp;
-    line_start_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile_off, p->d_ls, (uint32_t)(n_lines + 2), from);
-    MIC_TRY_DONE(hipGetLastError());
-    if (last != '\n') { nl = nb + 1; MIC_TRY_DONE(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
-    const unsigned gl = (unsigned)((n_lines + 1 + 255) / 256);
-    text_fasta_flag_kernel<<<gl, 256, 0, st>>>(raw, nb, p->d_ls, n_lines, d_flag);
-    MIC_TRY_DONE(hipcub::DeviceScan::ExclusiveSum(d_tmp2, tmp2, d_flag, d_rec, (int)(n_lines + 1), st));
-    uint32_t n_rec32 = 0;
-    MIC_TRY_DONE(hipMemcpyAsync(&n_rec32, d_rec + n_lines, 4, hipMemcpyDeviceToHost, st));
-    text_fasta_sample_kernel<<<gl, 256, 0, st>>>(p->d_ls, d_flag, d_rec, n_lines, p->stride, d_samples);
-    MIC_TRY_DONE(hipGetLastError());
-    MIC_TRY_DONE(hipStreamSynchronize(st));
-    p->n_rec = n_rec32;
-    if (n_rec32 == 0) { *status = PS_HEADER; goto done; }
-    const uint64_t n_samples = p->n_rec / p->stride + 2;
-    p->samples.assign(n_samples, (unsigned long long)nb);
-    const uint64_t have = (p->n_rec + p->stride - 1) / p->stride;          // samples the kernel wrote: records 0, stride, ...
-    MIC_TRY_DONE(hipMemcpy(p->samples.data(), d_samples, have * 8, hipMemcpyDeviceToHost));
-    goto done;
-  }
-  if (first != '@') { *status = PS_HEADER; goto done; }                       // (anything else: the host path)
-  if (n_lines % 4 != 0 || n_lines == 0) { *status = PS_LINES; goto done; }
-  {
-    const uint64_t n_rec = n_lines / 4;
-    p->n_rec = n_rec;
-    const uint64_t n_samples = n_rec / p->stride + 2;
-    const size_t b_ls = up((n_lines + 2) * 4), b_smp = up(n_samples * 8);
-    MIC_TRY_DONE(hipMalloc(&p->d_block, b_ls + b_smp));
-    p->d_ls = (uint32_t*)p->d_block;
-    unsigned long long* d_samples = (unsigned long long*)((char*)p->d_block + b_ls);
-    line_start_kernel<<<n_tiles, 256, 0, st>>>(raw, nb, d_tile_off, p->d_ls, (uint32_t)std::min<uint64_t>(n_lines + 2, 0xFFFFFFFFull), from);
-    MIC_TRY_DONE(hipGetLastError());
-    if (last != '\n') { nl = nb + 1; MIC_TRY_DONE(hipMemcpyAsync(p->d_ls + n_lines, &nl, 4, hipMemcpyHostToDevice, st)); }
-    p->samples.resize(n_samples);
-    text_sample_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(p->d_ls, nb, n_rec, p->stride, n_samples, d_samples);
-    MIC_TRY_DONE(hipGetLastError());
-    MIC_TRY_DONE(hipMemcpyAsync(p->samples.data(), d_samples, n_samples * 8, hipMemcpyDeviceToHost, st));
-    MIC_TRY_DONE(hipStreamSynchronize(st));
-    *n_used = p->samples.back() - from;
-  }
-done:
-  if (st) hipStreamSynchronize(st);
-  if (rc != MIC_OK || *status) { mic_text_free(e, p); return rc; }
-  *out = p; *n_records = p->n_rec;
-  return MIC_OK;
-}
-
-static bool text_offset(const mic_text* p, uint64_t r, unsigned long long& off) {
-  if (r == p->n_rec) { off = p->samples.back(); return true; }
-  if (r > p->n_rec || r % p->stride) return false;
-  off = p->samples[r / p->stride];
-  return true;
-}
-
-int mic_text_format(const mic_text* p) { return p ? (p->fasta ? '>' : '@') : 0; }
-
-int mic_text_offsets(const mic_text* p, const uint64_t** samples, size_t* n_samples, uint32_t* stride) {
-  if (!p || !samples || !n_samples || !stride) return mic_set_error(MIC_E_INVALID, "null argument");
-  *samples = (const uint64_t*)p->samples.data(); *n_samples = p->samples.size(); *stride = p->stride;
-  return MIC_OK;
-}
-
-int mic_text_to_slot(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, size_t slot_id, size_t* n_bytes) {
-  if (!e || !p || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  Ingest* g = ingest_with_slot(e, slot_id); if (!g) return MIC_E_STATE;
-  unsigned long long o0, o1;
-  if (r0 >= r1 || !text_offset(p, r0, o0) || !text_offset(p, r1, o1))
-    return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
-  if (o1 - o0 > g->max_bytes) return mic_set_error(MIC_E_INVALID, "text of %llu bytes does not fit the slot (%zu)", o1 - o0, g->max_bytes);
-  MIC_TRY(hipSetDevice(g->device));
-  Slot& s = g->slots[slot_id];
-  if (g->device != p->device) {
-    mic_peer_enable(g->device, p->device);      // (without peer access the runtime stages the copy through host memory)
-    MIC_TRY(hipMemcpyPeerAsync(s.d_raw, g->device, p->t + o0, p->device, (size_t)(o1 - o0), s.stream));
-  } else MIC_TRY(hipMemcpyAsync(s.d_raw, p->t + o0, (size_t)(o1 - o0), hipMemcpyDeviceToDevice, s.stream));
-  *n_bytes = (size_t)(o1 - o0);
-  return MIC_OK;
-}
-
-int mic_text_copy(mic_engine* e, mic_text* p, uint64_t r0, uint64_t r1, void* host_dst, size_t cap, size_t* n_bytes) {
-  if (!e || !p || !host_dst || !n_bytes) return mic_set_error(MIC_E_INVALID, "null argument");
-  unsigned long long o0, o1;
-  if (r0 >= r1 || !text_offset(p, r0, o0) || !text_offset(p, r1, o1))
-    return mic_set_error(MIC_E_INVALID, "records [%llu, %llu): not a range of whole strides", (unsigned long long)r0, (unsigned long long)r1);
-  *n_bytes = (size_t)(o1 - o0);
-  if (*n_bytes > cap) return mic_set_error(MIC_E_INVALID, "text of %zu bytes does not fit the buffer (%zu)", *n_bytes, cap);
-  MIC_TRY(hipSetDevice(p->device));
-  MIC_TRY(hipMemcpy(host_dst, p->t + o0, *n_bytes, hipMemcpyDeviceToHost));
   return MIC_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <time.h>
 
 #include "mi_clark.h"
 
@@ -276,6 +277,21 @@ int mic_hitmap_run(const MicTable& t, int slot_class, int n_cu, const uint32_t* 
                    const uint32_t* d_results, uint32_t n_targets, uint32_t* d_offsets, uint32_t* d_words, size_t cap_words, uint64_t* n_words,
                    hipStream_t s);
 
+// ---- the line indexer (mic_text.hip): bytes -> line ends per tile -> line starts ----------------------------------------------------
+// One text at a time, all work on stream s, nothing waits.  raw is 16-byte aligned (the kernels load 16 aligned bytes a thread) and
+// the text is its bytes [from, nb): an ingest slot's batch and the inflater's texts (mic_pairs_index_device) start at raw, from = 0;
+// a text at any other address counts from the 4-KiB boundary below it (mic_text_index_device).
+#define MIC_LINE_TILE 4096
+static inline uint32_t mic_line_tiles(uint32_t nb) { return (nb + MIC_LINE_TILE - 1) / MIC_LINE_TILE; }
+size_t mic_line_scan_bytes(size_t n_tiles);      // the scan storage mic_line_ends needs for a text of n_tiles tiles
+// line ends: d_tile[i] = the '\n' of tile i, d_tile_off = their exclusive sum (mic_line_tiles(nb) + 1 entries each, the last one the total)
+hipError_t mic_line_ends(const uint8_t* raw, uint32_t nb, uint32_t from, uint32_t* d_tile, uint32_t* d_tile_off, void* d_scan, size_t scan_bytes,
+                         hipStream_t s);
+// line starts: d_line_start[L] = offset from raw of the first byte of line L, for L < cap (line 0 starts at `from`)
+hipError_t mic_line_starts(const uint8_t* raw, uint32_t nb, uint32_t from, const uint32_t* d_tile_off, uint32_t* d_line_start, uint32_t cap,
+                           hipStream_t s);
+hipError_t mic_text_warm(hipStream_t s);         // loads the device code of mic_text.hip (a no-op kernel of that file)
+
 // ---- read splitting (mic_split.hip; the rule: mic_split.h) --------------------------------------------------------------------------
 // An engine's setting while mic_split_start is in force: every ingest batch it owns that returns MIC_INGEST_OK is partitioned.
 struct MicSplit {
@@ -338,6 +354,12 @@ MicKsketch* mic_engine_ksketch(mic_engine* e);
 MicHitmap* mic_engine_hitmap(mic_engine* e);
 uint32_t* mic_engine_min_quality(mic_engine* e);
 uint32_t* mic_engine_low_complexity(mic_engine* e);
+// (mic_ingest.hip defines this one) slot `slot_id` of e's ingest slots as mic_text.hip fills it: the slot's text buffer on the device
+// and its stream, the size and the device of e's slots; MIC_E_STATE with the error set when e has no such slot
+struct MicSlotText { uint8_t* d_raw; hipStream_t stream; size_t max_bytes; int device; };
+int mic_ingest_slot_text(mic_engine* e, size_t slot_id, MicSlotText* out);
+
+static inline double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec / 1e9; }
 
 // a failed HIP call sets the error text and returns its code / sets rc and jumps to the function's `done` label
 #define MIC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \

@@ -1,4 +1,4 @@
-// mic_qmask.h — the base-quality mask, one definition for host and device (mic_ingest.hip's pack_kernel<true> and
+// mic_qmask.h — the base-quality mask, one definition for host and device (mic_ingest.hip's pack_kernel<true>, mic_text.hip's
 // pair_merge_kernel<true>, mic_fastq_mask_quality, the command line's host merge of paired files).
 // A four-line FASTQ record has a sequence line S and a quality line U, both the bytes of the line without its '\n' (a '\r'
 // belongs to the line).  With the threshold byte c0 = offset + Q (mic_ingest_set_min_quality; 0 = off):

@@ -9,7 +9,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 if [ "${SAN:-address}" = thread ]; then SANF="-fsanitize=thread"; else SANF="-fsanitize=address,undefined -fno-sanitize-recover=undefined"; fi
 FLAGS="--offload-arch=gfx950 --offload-host-only -O1 -g -std=c++17 -fPIC $SANF -fno-omit-frame-pointer -Wno-unused-value -I$R/include -I$R/cuclark_amd/csrc"
 pids=()
-for f in mic_engine mic_kernels mic_ksketch mic_hitmap mic_build mic_synth mic_dbbuild mic_ingest mic_gz mic_abund mic_rollup mic_density mic_split; do
+for f in mic_engine mic_kernels mic_ksketch mic_hitmap mic_build mic_synth mic_dbbuild mic_ingest mic_text mic_gz mic_abund mic_rollup mic_density mic_split; do
   $HIPCC -x hip $FLAGS -c $R/cuclark_amd/csrc/$f.hip -o $OUT/$f.o & pids+=($!)
   if [ ${#pids[@]} -ge 4 ]; then wait ${pids[0]}; pids=("${pids[@]:1}"); fi
 done
