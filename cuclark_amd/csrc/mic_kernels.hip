@@ -1338,7 +1338,7 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     // a scalar branch around either form
     return __builtin_amdgcn_perm(up, raw, odd ? 0x05040706u : 0x03020504u);
   };
-  uint32_t cur_pp, cur_pe, cur_hdr, n_pp, n_pe, ahead_sel;
+  uint32_t cur_pp, cur_pe, cur_hdr, n_pp, n_pe;
   {
     const uint32_t r0 = wave0 < a.n_reads ? wave0 : a.n_reads - 1;
     cur_pp = __builtin_amdgcn_readfirstlane(a.reads_ptr[r0]); cur_pe = __builtin_amdgcn_readfirstlane(a.reads_ptr[r0 + 1]);
@@ -1347,8 +1347,10 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     __builtin_amdgcn_wave_barrier();
     ahead_take(ahead0, cur_pp, cur_hdr, n_pp, n_pe);
     ahead_issue(ahead1, n_pp, wave0 + 2 * n_waves, lane_copy());
-    ahead_sel = 1;
   }
+  // the entry of the read at hand and the entry of the read behind it; they change places per read (two pointers swapped: a selector
+  // cost a compare and a select at each of their five uses per read)
+  uint32_t *e_cur = ahead0, *e_nxt = ahead1;
   // Which instantiations run the software-pipelined road of the loop below: those with k and m as constants - the others are at
   // the register budget as they are (pipelined they spill into scratch memory and lose 10-17 %) and take every read through the
   // plain road.  MIC_R_PIPE: 0 none, 1 the two-strand table's only, 2 (default) the one-strand table's too.
@@ -1386,7 +1388,7 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
   // the sentinel of the positions past the read (no run continues across them; the stretch itself is one record whose lane the
   // set-up disables), and everything in front of and behind them has the windows, keys, runs and records it has per part.  The
   // joined front half is an instantiation of its own of `front` (gp: Gap instead of NoGap); the set-up of the pipelined road is
-  // shared and compares the record's k-mer with the junction's first position (see `step`): a one-part read pays that compare.
+  // shared and compares the record's k-mer with the junction's first position (see `take_up`): a one-part read pays that compare.
   struct NoGap {};
   struct Gap { uint32_t len1, b2, g0; };          // J2Shape's: nucleotides of part 1, u16 of part 2's first container in the entry, first junction position (~0: none)
   // front half of a chunk: window word, sampled positions, run records in LDS; returns the number of runs
@@ -1398,12 +1400,12 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     uint32_t wd;
     if constexpr (GAP) {
       // (the entry is 64 dwords: a lane past the window reads inside it whatever it computes - j2_dword(j < 12) + 1 <= 22)
-      const uint32_t* entry = ahead_sel ? ahead0 : ahead1;
+      const uint32_t* entry = e_cur;
       const uint32_t j = (uint32_t)ln < 12u ? (uint32_t)ln : 0u;
       const uint32_t d = j2_dword(j, gp.len1, gp.b2);
       wd = j2_window(ahead_word(entry, cur_pp), entry[d], entry[d + 1u], j, gp.len1, gp.b2);
     } else {
-      wd = use_ahead ? ahead_word(ahead_sel ? ahead0 : ahead1, cur_pp)
+      wd = use_ahead ? ahead_word(e_cur, cur_pp)
                      : window_word_w(cont, first, cend, base, ln, false, 0u);
     }
     wd_out = wd;
@@ -1719,42 +1721,114 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
     }
   };
 
-  // One step = one read taken up (N) and the read before it finished (P: its slots are on their way).  The loop below calls it
-  // with the two sets of registers in alternating roles: no copy of the run lanes' state from "next" to "pending".
-  uint32_t r = wave0; bool p_valid = false;
-  auto step = [&](Round& P, Round& N) __attribute__((always_inline)) -> bool {
-    const bool have = r < a.n_reads;
+  // ---- the loop over the wave's reads -----------------------------------------------------------------------------------------------
+  // The roads as POSITIONS IN THE CODE (round 12).  Until round 11 one `step` served every read: whether a read was pending
+  // (`p_valid`), whether there was a read at all (`have`) and which road it took (`shape`, `simple`) were values, each a 64-bit lane
+  // mask made by a select, tested through vcc and carried across the back half - two thirds of the kernel's scalar instructions were
+  // such glue.  Now the pipelined instantiations run a steady-state loop of their own, below: inside it a read is pending and the
+  // next one takes the pipelined road BY CONSTRUCTION; the one thing carried across the back half is the next read's number of runs,
+  // which the slot issue needs anyway and which doubles as the loop's condition (MIC_RMAX + 1: no such read).
+  uint32_t r = wave0;
+  // the read r on the plain road: every part, every chunk, every round one after the other, and the end of the read
+  auto plain_road = [&]() __attribute__((always_inline)) {
     uint32_t pp = cur_pp;
     const uint32_t pe = cur_pe;
-    // A read that is ONE part of at most 128 k-mers in the packer's format (its part ends where the read ends, or a 0 follows -
-    // the device packer's reservations, the generator's pitch; the header behind the part sits in the read-ahead entry for reads
-    // of up to ~170 nucleotides): no part loop, no chunk loop, the window out of the read-ahead entry.  The scalar unit (one
+    RowAcc acc; acc.label1 = 0; acc.count = 0;
+    uint32_t n_ent = 0, overflow = 0, total = 0, cg = MIC_CG_NONE;
+    auto chunk = [&](const uint32_t first, const uint32_t cend, const uint32_t base, const uint32_t nk, const bool use_ahead) __attribute__((always_inline)) {
+      uint32_t wd;
+      const uint32_t R = front(first, cend, base, nk, use_ahead, wd, NoGap{});
+      for (uint32_t rbase = 0; rbase < R; rbase += MIC_RMAX) {
+        Round L; uint32_t nrun;
+        setup(wd, rbase, R, L, nrun, NoGap{});
+        issue(L.cur, nrun, lane_copy());
+        consume(L, acc, n_ent, overflow, total, cg);
+      }
+    };
+    // A read that is ONE part of at most 128 k-mers in the packer's format (its part ends where the read ends - the device packer's
+    // reservations, the generator's pitch): no part loop, no chunk loop, the window out of the read-ahead entry.  The scalar unit (one
     // per CU) is what the kernel is short of, and the loops' bookkeeping is scalar work a 150-bp read does not need.
-    bool shape = false, simple = false;
-    uint32_t n_nrun = 0, plen0 = 0, pp1 = 0;
-    uint32_t slot2 = J2_NONE;                                 // the slot behind the first part, where the entry holds it (j2_slot2)
-    if (have) {
-      plen0 = cur_hdr; pp1 = pp + 1 + (plen0 + 7) / 8;
-      shape = plen0 - (uint32_t)k < 128u && pp1 == pe;       // (k <= plen0 < k + 128 by the unsigned wrap; pp1 == pe implies pp < pe)
-      if (!shape && plen0 - (uint32_t)k < 128u && pp1 < pe) {
-        const uint32_t rel = pp1 - cur_pp + (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);
-        if (rel < 24u) {
-          const uint32_t v = (ahead_sel ? ahead0 : ahead1)[rel >> 1];
-          slot2 = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu);
-          shape = slot2 == 0;
+    // (the straight line only where it is the common road: next to the pipelined road it would be a third copy of the back half)
+    const uint32_t plen0 = cur_hdr, pp1 = pp + 1 + (plen0 + 7) / 8;
+    if (!PIPE && plen0 - (uint32_t)k < 128u && pp1 == pe) chunk(pp + 1, pp1, 0u, plen0 - (uint32_t)k + 1u, true);   // (k <= plen0 < k + 128 by the unsigned wrap; pp1 == pe implies pp < pe)
+    else {
+      bool first_part = true;
+      while (pp < pe) {
+        // the header of a later part - for nearly every read the 0 that ends it - is among the 24 containers of the read-ahead
+        // entry more often than not: an LDS read instead of a global load the whole wave waits for
+        uint32_t plen;
+        {
+          const uint32_t rel = pp - cur_pp + (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);    // u16 offset inside the entry
+          if (first_part) plen = cur_hdr;
+          else if (rel < 24u) {
+            const uint32_t v = e_cur[rel >> 1];
+            plen = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu);
+          } else plen = __builtin_amdgcn_readfirstlane((uint32_t)cont[pp]);
+        }
+        const bool ahead_ok = first_part;
+        first_part = false;
+        if (plen == 0) break;
+        const uint32_t first = pp + 1;
+        pp = first + (plen + 7) / 8;
+        if (plen < (uint32_t)k) continue;
+        const uint32_t nk = plen - k + 1;
+        const uint32_t cend = pp;
+        for (uint32_t base = 0; base < nk; base += 128) chunk(first, cend, base, nk, ahead_ok && base == 0);
+      }
+    }
+    finish(acc, n_ent, total, overflow, r, cg);
+  };
+  // on to the next read: its read-ahead entry taken, the entry of the read three ahead asked for; returns the lane copy for `issue`
+  auto advance = [&]() __attribute__((always_inline)) -> int {
+    uint32_t t_hdr, t_pp, t_pe;
+    __builtin_amdgcn_wave_barrier();
+    ahead_take(e_nxt, n_pp, t_hdr, t_pp, t_pe);
+    __builtin_amdgcn_wave_barrier();
+    const int ln = lane_copy();                       // (one copy for the two of them: round 11)
+    ahead_issue(e_cur, t_pp, r + 3 * n_waves, ln);
+    { uint32_t* const e = e_cur; e_cur = e_nxt; e_nxt = e; }
+    cur_pp = n_pp; cur_pe = n_pe; cur_hdr = t_hdr; n_pp = t_pp; n_pe = t_pe;
+    r += n_waves;
+    return ln;
+  };
+  if constexpr (!PIPE) {
+    while (r < a.n_reads) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the read-ahead entry taken below)
+      plain_road();
+      advance();
+    }
+  } else {
+    // The read r taken up on the pipelined road, if it is one: front half and set-up into N.  Returns its number of runs, or
+    // MIC_RMAX + 1 for a read of the plain road (no k-mers, a long read, three or more parts, more than MIC_RMAX runs).
+    //  * ONE part of at most 128 k-mers in the packer's format (its part ends where the read ends; the header behind the part sits
+    //    in the read-ahead entry for reads of up to ~170 nucleotides), or in the terminated one (a 0 follows the part);
+    //  * two parts that fit one chunk, everything inside the read-ahead entry (j2_shape; scalar work): the same road, joined.
+    // ONE set-up behind either front half: with a set-up of its own for the joined read the run lanes' state would be merged from
+    // two sides, and the one-part road paid 14 v_mov per read for that merge.  So the set-up takes the junction's first position as
+    // a scalar - no position for a one-part read - and the one-part road pays one compare.
+    auto take_up = [&](Round& N) __attribute__((always_inline)) -> uint32_t {
+      const uint32_t pp = cur_pp, pe = cur_pe;
+      const uint32_t plen0 = cur_hdr, pp1 = pp + 1 + (plen0 + 7) / 8;
+      // (every decision a scalar compare and a branch of its own: `a && b` of two compares is built as two lane masks and an AND)
+      bool shape = false;
+      uint32_t slot2 = J2_NONE;                               // the slot behind the first part, where the entry holds it (j2_slot2)
+      if (__builtin_expect(plen0 - (uint32_t)k < 128u, 1)) {  // (k <= plen0 < k + 128 by the unsigned wrap)
+        if (__builtin_expect(pp1 == pe, 1)) shape = true;     // (pp1 == pe implies pp < pe)
+        else if (pp1 < pe) {
+          const uint32_t rel = pp1 - cur_pp + (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);
+          if (rel < 24u) {
+            const uint32_t v = e_cur[rel >> 1];
+            slot2 = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu);
+            shape = slot2 == 0;
+          }
         }
       }
-      // ONE set-up behind either front half: with a set-up of its own for the joined read the run lanes' state would be merged from
-      // three sides (two set-ups and, for a read of the plain road, what it held before), and the one-part road paid 14 v_mov per
-      // read for that merge.  So the set-up takes the junction's first position as a scalar - no position for a one-part read - and
-      // the one-part road pays one compare.
       uint32_t n_wd = 0, R = MIC_RMAX + 1u, g0 = 0xFFFFFFFFu;
-      if (PIPE && shape) {                                    // ... and at most one round of runs: the pipelined road
+      if (shape) {
         R = front(pp + 1, pp1, 0u, plen0 - (uint32_t)k + 1u, true, n_wd, NoGap{});
-      } else if constexpr (PIPE) {
-        // two parts that fit one chunk, everything inside the read-ahead entry (j2_shape; scalar work): the same road, joined
+      } else {
         const uint32_t odd = (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);
-        const uint32_t* entry = ahead_sel ? ahead0 : ahead1;
+        const uint32_t* entry = e_cur;
         const J2Shape j2 = j2_shape(plen0, slot2, pe - pp, odd, (uint32_t)k,
                                     [&](uint32_t u) { return (uint32_t)__builtin_amdgcn_readfirstlane(j2_half(entry[u >> 1], u)); });
         if (__builtin_expect(j2.ok != 0u, 0)) {
@@ -1762,75 +1836,54 @@ __global__ void __launch_bounds__(64 * MIC_M_WPB, 32 / MIC_M_WPB) query_kernel_r
           g0 = j2.g0;
         }
       }
-      if (PIPE && R <= MIC_RMAX) { setup(n_wd, 0u, R, N, n_nrun, Gap{0u, 0u, g0}); simple = true; }
-    }
-    // the earlier read: its slots have had the front half above to arrive
-    if (PIPE && p_valid) {
+      if (R <= MIC_RMAX) { uint32_t nrun; setup(n_wd, 0u, R, N, nrun, Gap{0u, 0u, g0}); }
+      else R = MIC_RMAX + 1u;
+      return R;
+    };
+    // the back half of the pending read P (its slots have had the next read's front half to arrive), and the end of that read
+    auto back_half = [&](Round& P) __attribute__((always_inline)) {
       RowAcc acc; acc.label1 = 0; acc.count = 0;
       uint32_t n_ent = 0, overflow = 0, total = 0, cg = MIC_CG_NONE;
       consume(P, acc, n_ent, overflow, total, cg);
       finish(acc, n_ent, total, overflow, r - n_waves, cg);  // (a pending read is the one before this one)
-    } else {
+    };
+    // One half of the steady-state loop's body: the read r taken up into N while P is pending, P's back half (half_in), then N's slots
+    // asked for (half_out) - N is the pending read of the other half.  More than MIC_RMAX runs: there is no read r, or it is one of the
+    // plain road; nothing is pending.
+    // (two lambdas and the test between them in the loop itself: a bool returned out of one lambda is merged into a flag again)
+    auto half_in = [&](Round& P, Round& N) __attribute__((always_inline)) -> uint32_t {
+      uint32_t R = MIC_RMAX + 1u;
+      if (r < a.n_reads) R = take_up(N);
+      asm volatile("" : "+s"(R));                             // (the number of runs itself is what lives across the back half, not a flag derived from it)
+      back_half(P);
+      return R;
+    };
+    auto half_out = [&](Round& N, const uint32_t R) __attribute__((always_inline)) {
+      const int ln = advance();
+      issue(N.cur, R, ln);
+    };
+    Round Ra, Rb;
+    while (r < a.n_reads) {                                   // nothing is pending here
+      const uint32_t R = take_up(Ra);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the read-ahead entry taken below)
-    }
-    if (!have) return false;
-    if (!simple) {
-      RowAcc acc; acc.label1 = 0; acc.count = 0;
-      uint32_t n_ent = 0, overflow = 0, total = 0, cg = MIC_CG_NONE;
-      auto chunk = [&](const uint32_t first, const uint32_t cend, const uint32_t base, const uint32_t nk, const bool use_ahead) __attribute__((always_inline)) {
-        uint32_t wd;
-        const uint32_t R = front(first, cend, base, nk, use_ahead, wd, NoGap{});
-        for (uint32_t rbase = 0; rbase < R; rbase += MIC_RMAX) {
-          Round L; uint32_t nrun;
-          setup(wd, rbase, R, L, nrun, NoGap{});
-          issue(L.cur, nrun, lane_copy());
-          consume(L, acc, n_ent, overflow, total, cg);
+      if (R <= MIC_RMAX) {
+        const int ln = advance();
+        issue(Ra.cur, R, ln);
+        for (;;) {                                            // the two sets of registers in alternating roles: no copy from "next" to "pending"
+          const uint32_t Rn = half_in(Ra, Rb);
+          if (Rn > MIC_RMAX) break;
+          half_out(Rb, Rn);
+          const uint32_t Rm = half_in(Rb, Ra);
+          if (Rm > MIC_RMAX) break;
+          half_out(Ra, Rm);
         }
-      };
-      // (the straight line only where it is the common road: next to the pipelined road it would be a third copy of the back half)
-      if (!PIPE && shape) chunk(pp + 1, pp1, 0u, plen0 - (uint32_t)k + 1u, true);
-      else {
-        bool first_part = true;
-        while (pp < pe) {
-          // the header of a later part - for nearly every read the 0 that ends it - is among the 24 containers of the read-ahead
-          // entry more often than not: an LDS read instead of a global load the whole wave waits for
-          uint32_t plen;
-          {
-            const uint32_t rel = pp - cur_pp + (uint32_t)((((uint64_t)(cont + cur_pp)) >> 1) & 1);    // u16 offset inside the entry
-            if (first_part) plen = cur_hdr;
-            else if (rel < 24u) {
-              const uint32_t v = (ahead_sel ? ahead0 : ahead1)[rel >> 1];
-              plen = __builtin_amdgcn_readfirstlane((rel & 1u) ? v >> 16 : v & 0xFFFFu);
-            } else plen = __builtin_amdgcn_readfirstlane((uint32_t)cont[pp]);
-          }
-          const bool ahead_ok = first_part;
-          first_part = false;
-          if (plen == 0) break;
-          const uint32_t first = pp + 1;
-          pp = first + (plen + 7) / 8;
-          if (plen < (uint32_t)k) continue;
-          const uint32_t nk = plen - k + 1;
-          const uint32_t cend = pp;
-          for (uint32_t base = 0; base < nk; base += 128) chunk(first, cend, base, nk, ahead_ok && base == 0);
-        }
+        if (!(r < a.n_reads)) break;
       }
-      finish(acc, n_ent, total, overflow, r, cg);
+      plain_road();
+      advance();
     }
-    uint32_t t_hdr, t_pp, t_pe;
-    __builtin_amdgcn_wave_barrier();
-    ahead_take(ahead_sel ? ahead1 : ahead0, n_pp, t_hdr, t_pp, t_pe);
-    __builtin_amdgcn_wave_barrier();
-    const int ln = lane_copy();                       // (one copy for the two of them: round 11)
-    ahead_issue(ahead_sel ? ahead0 : ahead1, t_pp, r + 3 * n_waves, ln);
-    ahead_sel ^= 1;
-    cur_pp = n_pp; cur_pe = n_pe; cur_hdr = t_hdr; n_pp = t_pp; n_pe = t_pe;
-    p_valid = simple;
-    if (simple) issue(N.cur, n_nrun, ln);
-    r += n_waves;
-    return true;
-  };
-  Round Ra, Rb;
-  while (step(Ra, Rb) && step(Rb, Ra)) {}
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (a read-ahead entry on its way into LDS: the wave does not end before it has landed)
 }
 
 // ---- crowded runs: the follow-up of query_kernel_r ---------------------------------------------------------------------------------
