@@ -183,6 +183,11 @@ SYMBOLS = [
     ("mic_kraken_stop", C.c_int, [_VP]),
     ("mic_ingest_kraken_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     ("mic_kraken_format", C.c_long, [_VP, _SZ, _VP, _VP, C.c_int, C.c_uint32, C.POINTER(MicAbundFilter), _VP, _VP, _VP, C.c_char_p, _SZ]),
+    ("mic_db_census_enable", C.c_int, [_VP, C.c_int]),
+    ("mic_db_census_fetch", C.c_int, [_VP, _VP, _SZ, _VP]),
+    ("mic_db_census_device", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_int, _VP, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, _VP]),
+    ("mic_db_census_host", C.c_int, [_VP, C.c_uint64, _VP, C.c_int, _VP, C.c_uint32, C.c_int, C.c_uint32, _VP, _VP]),
+    ("mic_kcoverage_format", C.c_long, [_VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_char_p, _SZ]),
     ("mic_split_start", C.c_int, [_VP, C.POINTER(MicAbundFilter), C.c_int]),
     ("mic_split_stop", C.c_int, [_VP]),
     ("mic_ingest_split_text", C.c_int, [_VP, _SZ, C.POINTER(_VP), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_VP),

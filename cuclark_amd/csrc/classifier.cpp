@@ -198,6 +198,8 @@ Classifier::Classifier(const Options& opt) : opt_(opt) {
     check(mic_create(&cfg, &e), "engine creation");
     engines_.push_back(e);
     if (parts_ > 1) check(mic_db_set_part(e, (uint32_t)(d % parts_), (uint32_t)parts_), "table part");
+    // --kmer-coverage: the first engine counts the table it builds (with -d N the tables are replicas)
+    if (covering() && engines_.size() == 1) check(mic_db_census_enable(e, 1), "table census");
     // --min-base-quality: every engine masks on its device - in the packer for four-line FASTQ, in the pair merge for two inflated mates
     if (opt_.min_quality_byte) check(mic_ingest_set_min_quality(e, opt_.min_quality_byte), "base-quality threshold");
     // --mask-low-complexity: every engine masks the batches it owns on its device, in front of the packer
@@ -327,6 +329,13 @@ void Classifier::ksketch_result(std::vector<uint8_t>& regs, std::vector<uint64_t
     for (size_t i = 0; i < r.size(); ++i) if (r[i] > regs[i]) regs[i] = r[i];
     for (size_t i = 0; i < T; ++i) hits[i] += h[i];
   }
+}
+
+std::vector<uint64_t> Classifier::census_counts() {
+  std::vector<uint64_t> counts(names_.size(), 0);
+  uint64_t stats[8];
+  check(mic_db_census_fetch(engines_[0], counts.data(), counts.size(), stats), "table census");
+  return counts;
 }
 
 std::vector<uint64_t> Classifier::rollup_counts() {
@@ -488,7 +497,8 @@ void Classifier::run(const std::string& objects, const std::string& results) {
     return;
   }
   // list-of-files mode: objects and results name two parallel lists (CuCLARK_hh.hh:413-427)
-  if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
+  if (covering()) die("--kmer-coverage does not take list-of-files mode: classify the files one at a time.");
+  if (!opt_.kmer_report.empty()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
   if (mapping()) die(std::string(map_option()) + " does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");
@@ -572,7 +582,8 @@ void Classifier::run_paired(const std::string& f1, const std::string& f2, const 
     list_mode = !((!line.empty() && (line[0] == '>' || line[0] == '@')) || ele.size() == 2);
   }
   if (!list_mode) { one(f1, f2, results, false); return; }
-  if (sketching()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
+  if (covering()) die("--kmer-coverage does not take list-of-files mode: classify the files one at a time.");
+  if (!opt_.kmer_report.empty()) die("--kmer-report does not take list-of-files mode: classify the files one at a time.");
   if (mapping()) die(std::string(map_option()) + " does not take list-of-files mode: classify the files one at a time.");
   if (counting()) die("--abundance does not take list-of-files mode: classify the files with -R and run estimate_abundance -F on the result files.");
   if (ranking()) die("--rank-report does not take list-of-files mode: classify the files with -R --extended and run estimate_abundance -F --rank-report on the result files.");

@@ -38,6 +38,7 @@ struct Options {
   std::string rank_report, lineage;                          // --rank-report <file> [--lineage <tsv>]: the rank roll-up is counted (mic_rollup_*)
   std::string density;                                       // --density <file>: the score densities are counted (mic_density_*)
   std::string kmer_report;                                   // --kmer-report <file>: distinct k-mers hit per target are sketched (mic_ksketch_*)
+  std::string kmer_coverage;                                 // --kmer-coverage <file>: the same sketches, and the census of the first engine's table (mic_db_census_*)
   uint32_t min_quality_byte = 0;                             // --min-base-quality Q [--quality-offset 33|64]: offset + Q, 0 = off (mic_qmask.h)
   std::string classified_out, unclassified_out;              // --classified-out / --unclassified-out <file>: the reads themselves, split (mic_split_*)
   std::string hit_maps;                                      // --hit-maps <file>: per read the runs of k-mer assignments along it (mic_hitmap_*)
@@ -102,6 +103,8 @@ class Classifier {
   std::vector<uint64_t> density_counts();
   // --kmer-report: the run's sketches (csrc/mic_ksketch.h), the engines' merged: registers by max, hits by sum
   void ksketch_result(std::vector<uint8_t>& regs, std::vector<uint64_t>& hits);
+  // --kmer-coverage: the k-mers of every target in the resident table (csrc/mic_census.h), counted when the first engine loaded it
+  std::vector<uint64_t> census_counts();
   const rank::Lineage& lineage() const { return lineage_; }
 
   // --classified-out / --unclassified-out: is `objects` with `results` a list-of-files run?  (no device needed: asked before one is touched)
@@ -139,7 +142,8 @@ class Classifier {
   // (--kmer-report prints the reads --abundance gives every target: it starts the same counters)
   // (--kraken-report is formatted from the same counters)
   bool counting() const { return !opt_.abundance.empty() || !opt_.kraken_report.empty() || sketching(); }
-  bool sketching() const { return !opt_.kmer_report.empty(); }
+  bool sketching() const { return !opt_.kmer_report.empty() || covering(); }
+  bool covering() const { return !opt_.kmer_coverage.empty(); }
   bool ranking() const { return !opt_.rank_report.empty(); }
   bool densing() const { return !opt_.density.empty(); }
   // --classified-out / --unclassified-out: the classes asked for (0: none).  The streaming path takes the split text from the engines

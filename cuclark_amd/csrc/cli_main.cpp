@@ -81,6 +81,12 @@ static void print_usage(const char* prog) {
                "                     counts into <file>: %, clade reads, taxon reads, rank code, taxid, indented name.  The tree is the lineage of\n"
                "                     --rank-report (from <tsv>, else <DB>/../taxonomy; with neither the targets hang under the root); the targets\n"
                "                     get the code of <rank> (default species); works without -R like --abundance\n";
+  std::cout << "--kmer-coverage <file>, the k-mer report with two more columns: Name,Reads,Kmers,DistinctKmers,Duplication,TargetKmers,Coverage -\n"
+               "                     TargetKmers, the target's k-mers in the resident table, from a census of the table on the device when it is\n"
+               "                     loaded (every k-mer of the database is probed through the table; one that does not come back under its label\n"
+               "                     fails the load), and Coverage = min(DistinctKmers, TargetKmers) / TargetKmers: the fraction of the target the\n"
+               "                     objects touched; with -s the coverage is relative to the sampled (resident) k-mers; alone or next to\n"
+               "                     --kmer-report and -R; not with --db-sharded or a list of files\n";
   std::cout << "--classified-out <file>,  also write the objects that are assigned under --min-confidence / --min-gamma into <file>, as they are in -O\n";
   std::cout << "--unclassified-out <file>,  also write the other objects (no hit, or dropped by the filter) into <file>; either option alone or both;\n"
                "                     one -O input only (not -P, not a list of files); the names are taken as given; work without -R like --abundance\n";
@@ -182,7 +188,7 @@ int main(int argc, char** argv) {
   bool db_sharded = false;
   size_t parts = 0;
   int i_targets = -1, i_objects = -1, i_objects2 = -1, i_folder = -1, i_results = -1;
-  std::string abundance, rank_report, lineage, density, kmer_report, classified_out, unclassified_out, hit_maps, kraken_out, kraken_report, kraken_rank = "species";
+  std::string abundance, rank_report, lineage, density, kmer_report, kmer_coverage, classified_out, unclassified_out, hit_maps, kraken_out, kraken_report, kraken_rank = "species";
   mic_abund_filter ab_filter = {5, 10, 0, 1};
   uint64_t ab_min_num = 0, ab_min_den = 1;
   long min_q = 0, q_offset = 0;          // --min-base-quality, --quality-offset (0: not given)
@@ -233,6 +239,7 @@ int main(int argc, char** argv) {
     if (val == "--classified-out") { need("Please specify the file of the classified objects!"); classified_out = argv[i]; if (classified_out.empty()) { std::cerr << "Please specify the file of the classified objects!" << std::endl; exit(1); } continue; }
     if (val == "--unclassified-out") { need("Please specify the file of the unclassified objects!"); unclassified_out = argv[i]; if (unclassified_out.empty()) { std::cerr << "Please specify the file of the unclassified objects!" << std::endl; exit(1); } continue; }
     if (val == "--density") { need("Please specify the file of the density report!"); density = argv[i]; continue; }
+    if (val == "--kmer-coverage") { need("Please specify the file of the k-mer coverage report!"); kmer_coverage = argv[i]; if (kmer_coverage.empty()) { std::cerr << "Please specify the file of the k-mer coverage report!" << std::endl; exit(1); } continue; }
     if (val == "--kmer-report") { need("Please specify the file of the k-mer report!"); kmer_report = argv[i]; if (kmer_report.empty()) { std::cerr << "Please specify the file of the k-mer report!" << std::endl; exit(1); } continue; }
     if (val == "--hit-maps") { need("Please specify the file of the hit maps!"); hit_maps = argv[i]; if (hit_maps.empty()) { std::cerr << "Please specify the file of the hit maps!" << std::endl; exit(1); } continue; }
     if (val == "--kraken-out") { need("Please specify the file of the Kraken output!"); kraken_out = argv[i]; if (kraken_out.empty()) { std::cerr << "Please specify the file of the Kraken output!" << std::endl; exit(1); } continue; }
@@ -362,12 +369,23 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
+  if (!kmer_coverage.empty()) {      // refused before any device is touched
+    if (db_sharded) { std::cerr << "--kmer-coverage does not take --db-sharded: the sketches and the census are counted behind one GPU's whole table." << std::endl; exit(1); }
+    for (int io : {i_objects, i_objects2})
+      if (io >= 0 && same_file(kmer_coverage, argv[io])) { std::cerr << "--kmer-coverage would overwrite the input: " << kmer_coverage << std::endl; exit(1); }
+    if (i_results >= 0 && same_file(kmer_coverage, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kmer-coverage would overwrite the result CSV: " << kmer_coverage << std::endl; exit(1); }
+    if (same_file(kmer_coverage, kmer_report)) { std::cerr << "--kmer-coverage names the file of another output: " << kmer_coverage << std::endl; exit(1); }
+    if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
+      std::cerr << "--kmer-coverage does not take list-of-files mode: classify the files one at a time." << std::endl;
+      exit(1);
+    }
+  }
   if (!hit_maps.empty()) {      // refused before any device is touched
     if (db_sharded) { std::cerr << "--hit-maps does not take --db-sharded: a map is the labels of one GPU's whole table along the object." << std::endl; exit(1); }
     for (int io : {i_objects, i_objects2})
       if (io >= 0 && same_file(hit_maps, argv[io])) { std::cerr << "--hit-maps would overwrite the input: " << hit_maps << std::endl; exit(1); }
     if (i_results >= 0 && same_file(hit_maps, std::string(argv[i_results]) + ".csv")) { std::cerr << "--hit-maps would overwrite the result CSV: " << hit_maps << std::endl; exit(1); }
-    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out})
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &kmer_coverage, &classified_out, &unclassified_out})
       if (same_file(hit_maps, *f)) { std::cerr << "--hit-maps names the file of another output: " << hit_maps << std::endl; exit(1); }
     if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
       std::cerr << "--hit-maps does not take list-of-files mode: classify the files one at a time." << std::endl;
@@ -380,7 +398,7 @@ int main(int argc, char** argv) {
     for (int io : {i_objects, i_objects2})
       if (io >= 0 && same_file(kraken_out, argv[io])) { std::cerr << "--kraken-out would overwrite the input: " << kraken_out << std::endl; exit(1); }
     if (i_results >= 0 && same_file(kraken_out, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kraken-out would overwrite the result CSV: " << kraken_out << std::endl; exit(1); }
-    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out, &kraken_report})
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &kmer_coverage, &classified_out, &unclassified_out, &kraken_report})
       if (same_file(kraken_out, *f)) { std::cerr << "--kraken-out names the file of another output: " << kraken_out << std::endl; exit(1); }
     if (i_objects >= 0 && i_results >= 0 && mic::Classifier::list_mode(argv[i_objects], argv[i_results])) {
       std::cerr << "--kraken-out does not take list-of-files mode: classify the files one at a time." << std::endl;
@@ -391,7 +409,7 @@ int main(int argc, char** argv) {
     for (int io : {i_objects, i_objects2})
       if (io >= 0 && same_file(kraken_report, argv[io])) { std::cerr << "--kraken-report would overwrite the input: " << kraken_report << std::endl; exit(1); }
     if (i_results >= 0 && same_file(kraken_report, std::string(argv[i_results]) + ".csv")) { std::cerr << "--kraken-report would overwrite the result CSV: " << kraken_report << std::endl; exit(1); }
-    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &classified_out, &unclassified_out, &hit_maps})
+    for (const std::string* f : {&abundance, &rank_report, &density, &kmer_report, &kmer_coverage, &classified_out, &unclassified_out, &hit_maps})
       if (same_file(kraken_report, *f)) { std::cerr << "--kraken-report names the file of another output: " << kraken_report << std::endl; exit(1); }
   }
   if (split) {      // refused before any device is touched
@@ -406,11 +424,11 @@ int main(int argc, char** argv) {
       exit(1);
     }
   }
-  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || !hit_maps.empty() || !kraken_out.empty() || !kraken_report.empty() || split) && i_results < 0 && ext) {
+  if ((!abundance.empty() || !rank_report.empty() || !density.empty() || !kmer_report.empty() || !kmer_coverage.empty() || !hit_maps.empty() || !kraken_out.empty() || !kraken_report.empty() || split) && i_results < 0 && ext) {
     std::cerr << "--extended writes the result CSV: it needs -R <fileResults>." << std::endl;
     exit(1);
   }
-  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && hit_maps.empty() && kraken_out.empty() && kraken_report.empty() && !split)) {
+  if (i_targets < 0 || i_folder < 0 || i_objects < 0 || (i_results < 0 && abundance.empty() && rank_report.empty() && density.empty() && kmer_report.empty() && kmer_coverage.empty() && hit_maps.empty() && kraken_out.empty() && kraken_report.empty() && !split)) {
     std::cerr << "Failed to run " << argv[0] << ": at least four  parameters are necessary";
     std::cerr << ": file of targets, directory of database, file of objects, file for results." << std::endl;
     print_usage(argv[0]);
@@ -431,6 +449,7 @@ int main(int argc, char** argv) {
   o.rank_report = rank_report; o.lineage = lineage;
   o.density = density;
   o.kmer_report = kmer_report;
+  o.kmer_coverage = kmer_coverage;
   o.hit_maps = hit_maps;
   o.kraken_out = kraken_out; o.kraken_report = kraken_report;
   o.classified_out = classified_out; o.unclassified_out = unclassified_out;
@@ -492,6 +511,24 @@ int main(int argc, char** argv) {
       if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
         throw std::runtime_error("Failed to write the k-mer report: " + kmer_report);
       std::cout << " - K-mer report stored in " << kmer_report << std::endl;
+    }
+    if (!kmer_coverage.empty()) {
+      std::vector<uint8_t> regs;
+      std::vector<uint64_t> hits;
+      classifier->ksketch_result(regs, hits);
+      const std::vector<uint64_t> ab = classifier->abundance_counts();
+      const std::vector<uint64_t> tk = classifier->census_counts();
+      const std::vector<std::string>& names = classifier->target_names();
+      std::vector<const char*> nm(names.size());
+      for (size_t t = 0; t < names.size(); ++t) nm[t] = names[t].c_str();
+      std::string report;
+      uint32_t bad = 0;
+      if (!mic::ksketch::format_coverage(nm.data(), ab.data() + 2, regs.data(), hits.data(), tk.data(), (uint32_t)names.size(), report, &bad))
+        throw std::runtime_error("--kmer-coverage: the objects hit k-mers of " + names[bad] + ", of which the table census counted none");
+      FILE* f = fopen(kmer_coverage.c_str(), "wb");
+      if (!f || fwrite(report.data(), 1, report.size(), f) != report.size() || fclose(f) != 0)
+        throw std::runtime_error("Failed to write the k-mer coverage report: " + kmer_coverage);
+      std::cout << " - K-mer coverage report stored in " << kmer_coverage << std::endl;
     }
   } catch (const std::exception& ex) {
     std::cerr << ex.what() << std::endl;

@@ -7,6 +7,7 @@
 //     DistinctKmers  llround of the estimate from the target's registers, at least 1
 //     Duplication    Kmers / DistinctKmers, two decimals, rounded half up from integer arithmetic
 // A target with many reads and a high duplication was hit in the same few k-mers over and over.
+// format_coverage (below): the same lines with the target's k-mers in the table and the fraction of them the reads touched.
 #ifndef MIC_KMER_REPORT_HPP
 #define MIC_KMER_REPORT_HPP
 
@@ -66,6 +67,26 @@ inline std::string format_report(const char* const* names, const uint64_t* reads
     out += std::string(names[t]) + "," + num(reads[t]) + "," + num(hits[t]) + "," + num(d) + "," + decimal::ratio_text(hits[t], d, 2) + "\n";
   }
   return out;
+}
+
+// The coverage report of exe/cuCLARK --kmer-coverage and mic_kcoverage_format: the k-mer report's lines and two more columns,
+//   Name,Reads,Kmers,DistinctKmers,Duplication,TargetKmers,Coverage
+//     TargetKmers    the target's k-mers in the resident table (the census counts, csrc/mic_census.h)
+//     Coverage       min(DistinctKmers, TargetKmers) / TargetKmers, six decimals, rounded half up from integer arithmetic (the clamp:
+//                    a HyperLogLog estimate may exceed the true total by its error)
+// target_kmers: n_targets words.  A target with hits and no k-mers in the table (no healthy table gives one): false, *bad = the target.
+inline bool format_coverage(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, const uint64_t* target_kmers,
+                            uint32_t n_targets, std::string& out, uint32_t* bad = nullptr) {
+  out = "Name,Reads,Kmers,DistinctKmers,Duplication,TargetKmers,Coverage\n";
+  auto num = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  for (uint32_t t = 0; t < n_targets; ++t) {
+    if (!hits[t]) continue;
+    if (!target_kmers[t]) { if (bad) *bad = t; return false; }
+    const uint64_t d = distinct(regs + (size_t)t * MIC_KSKETCH_REGS, hits[t]);
+    out += std::string(names[t]) + "," + num(reads[t]) + "," + num(hits[t]) + "," + num(d) + "," + decimal::ratio_text(hits[t], d, 2) + "," +
+           num(target_kmers[t]) + "," + decimal::ratio_text(d < target_kmers[t] ? d : target_kmers[t], target_kmers[t], 6) + "\n";
+  }
+  return true;
 }
 
 }  // namespace ksketch

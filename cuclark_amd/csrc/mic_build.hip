@@ -8,6 +8,7 @@
 //   C  slot construction (reachability filter, chain layout)
 #include "mic_internal.h"
 #include "mic_device.h"
+#include "mic_buckets.h"     // TILE, TileA, block_scan2, kept_bucket, raw_key: shared with the census
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,32 +18,9 @@
 
 #include <hipcub/hipcub.hpp>
 
-#define TILE 256
-
 namespace {
 
-struct TileA { unsigned long long elems; unsigned long long nonzero; };
 struct TileB { unsigned long long ovf_slots; unsigned long long kept; unsigned int max_bucket; unsigned int pad; };
-
-// exclusive scan of (a,b) pairs over a 256-thread block; returns this thread's exclusive prefix and the
-// block totals through tot_a/tot_b.
-__device__ inline void block_scan2(uint32_t a, uint32_t b, uint32_t& ex_a, uint32_t& ex_b, uint32_t& tot_a,
-                                   uint32_t& tot_b) {
-  __shared__ uint32_t sa[TILE], sb[TILE];
-  const int t = threadIdx.x;
-  sa[t] = a; sb[t] = b;
-  __syncthreads();
-  for (int off = 1; off < TILE; off <<= 1) {
-    uint32_t va = 0, vb = 0;
-    if (t >= off) { va = sa[t - off]; vb = sb[t - off]; }
-    __syncthreads();
-    sa[t] += va; sb[t] += vb;
-    __syncthreads();
-  }
-  ex_a = sa[t] - a; ex_b = sb[t] - b;
-  tot_a = sa[TILE - 1]; tot_b = sb[TILE - 1];
-  __syncthreads();
-}
 
 __global__ void __launch_bounds__(TILE) tile_a_kernel(const uint8_t* __restrict__ sizes, uint64_t n, TileA* out) {
   uint64_t i = (uint64_t)blockIdx.x * TILE + threadIdx.x;
@@ -50,11 +28,6 @@ __global__ void __launch_bounds__(TILE) tile_a_kernel(const uint8_t* __restrict_
   uint32_t ea, eb, ta, tb;
   block_scan2(sz, sz > 0, ea, eb, ta, tb);
   if (threadIdx.x == 0) { out[blockIdx.x].elems = ta; out[blockIdx.x].nonzero = tb; }
-}
-
-__device__ inline bool kept_bucket(uint32_t sz, uint64_t rank_incl, uint32_t sampling) {
-  // CuClarkDB.cu:508-519: choice = (all || nbNonZeroBuckets % mod == 0) ? keep : skip, counted over non-empty buckets
-  return sz > 0 && (sampling <= 1 || (rank_incl % sampling) == 0);
 }
 
 template <int CAP>
@@ -80,9 +53,6 @@ __global__ void __launch_bounds__(TILE) tile_b_kernel(const uint8_t* __restrict_
     out[blockIdx.x].ovf_slots = t1; out[blockIdx.x].kept = t2; out[blockIdx.x].max_bucket = smax; out[blockIdx.x].pad = 0;
   }
 }
-
-template <typename RAW>
-__device__ inline uint64_t raw_key(const void* keys, uint64_t i) { return (uint64_t)((const RAW*)keys)[i]; }
 
 // Emits the chain of one bucket.  Reachable entries are visited twice (count, then emit).
 template <typename RAW, bool KEY64>
@@ -201,6 +171,35 @@ int mic_reduce_sizes(const uint8_t* d_sizes, uint64_t n, uint64_t* total, uint64
   hipFree(d);
   if (e != hipSuccess) return -4;
   *total = h[0]; *nonzero = h[1];
+  return 0;
+}
+
+// pass A alone, for the census (mic_kernels.hip: mic_launch_census): per 256-bucket tile the elements and the non-empty buckets
+// in front of it (the builders' TileA bases), in a device allocation the caller frees.  0, or -3 (no memory) / -4 (HIP error).
+int mic_tile_bases(const uint8_t* d_sizes, uint64_t n_buckets, void** d_bases, hipStream_t s) {
+  const uint64_t n_tiles = (n_buckets + TILE - 1) / TILE;
+  *d_bases = nullptr;
+  if (n_buckets == 0 || n_tiles > 0x7fffffffULL) return -1;
+  TileA* d_a = nullptr;
+  std::vector<TileA> h_a(n_tiles);
+  hipError_t e = hipMalloc(&d_a, sizeof(TileA) * n_tiles);
+  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? -3 : -4; }
+  tile_a_kernel<<<(unsigned)n_tiles, TILE, 0, s>>>(d_sizes, n_buckets, d_a);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h_a.data(), d_a, sizeof(TileA) * n_tiles, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) {
+    uint64_t tot_elems = 0, tot_nz = 0;
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+      const uint64_t el = h_a[t].elems, z = h_a[t].nonzero;
+      h_a[t].elems = tot_elems; h_a[t].nonzero = tot_nz;
+      tot_elems += el; tot_nz += z;
+    }
+    e = hipMemcpyAsync(d_a, h_a.data(), sizeof(TileA) * n_tiles, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);      // (h_a leaves with this frame)
+  }
+  if (e != hipSuccess) { hipStreamSynchronize(s); hipFree(d_a); (void)hipGetLastError(); return -4; }
+  *d_bases = d_a;
   return 0;
 }
 

@@ -3,6 +3,7 @@
 // mic_build.hip.  Mirrors the public surface of CuClarkDB<HKMERr> (CuClarkDB.cuh:98-150).
 #include "mi_clark.h"
 #include "mic_internal.h"
+#include "mic_census.h"
 
 #include <errno.h>
 #include <stdarg.h>
@@ -158,6 +159,7 @@ struct mic_engine {
   MicSplit split;                   // mic_split_start / _stop: the engine's read-splitting setting (mic_split.hip)
   MicKsketch ksketch;               // mic_ksketch_*: the engine's k-mer sketches (mic_ksketch.hip)
   MicHitmap hitmap;                 // mic_hitmap_start / _stop: the engine's hit-map setting (mic_hitmap.hip)
+  MicCensus census;                 // mic_db_census_*: the loaded table's census (mic_census.h)
 };
 
 namespace {
@@ -409,6 +411,38 @@ int apply_part(const mic_engine* e, uint64_t htsize, uint64_t& s0, uint64_t& s1)
   return MIC_OK;
 }
 
+// the census of the table just built (mic_census.h), while the images it was built from are still on the device: every k-mer the
+// builders enumerated is probed through the resident table.  A k-mer that does not come back under its label fails the load.
+int run_census(mic_engine* e, const uint8_t* d_sizes_shard, uint64_t htsize, uint64_t s0, uint64_t s1, const void* d_keys_shard, int key_bytes,
+               const uint16_t* d_labels_shard, uint32_t sampling, uint64_t rank_base) {
+  MicCensus& c = e->census;
+  const uint32_t T = e->cfg.num_targets;
+  struct timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+  void* d_bases = nullptr;
+  int rc = MIC_OK;
+  c.have = false;
+  c.counts.assign(T, 0);
+  if (c.d_counts) { hipFree(c.d_counts); c.d_counts = nullptr; }
+  MIC_TRY_DONE(hipMalloc(&c.d_counts, (size_t)T * 8 + 64));
+  MIC_TRY_DONE(hipMemsetAsync(c.d_counts, 0, (size_t)T * 8 + 64, e->stream));
+  { const int br = mic_tile_bases(d_sizes_shard, s1 - s0, &d_bases, e->stream);
+    if (br) { rc = mic_set_error(br == -3 ? MIC_E_NOMEM : MIC_E_HIP, "table census: the tile bases failed (%d)", br); goto done; } }
+  MIC_TRY_DONE(mic_launch_census(e->table, e->slot_class, d_sizes_shard, s1 - s0, s0, htsize, d_keys_shard, key_bytes, d_labels_shard, d_bases,
+                                 sampling, rank_base, T, c.d_counts, c.d_counts + T, e->stream));
+  if (T) MIC_TRY_DONE(hipMemcpyAsync(c.counts.data(), c.d_counts, (size_t)T * 8, hipMemcpyDeviceToHost, e->stream));
+  MIC_TRY_DONE(hipMemcpyAsync(c.stats, c.d_counts + T, 64, hipMemcpyDeviceToHost, e->stream));
+  MIC_TRY_DONE(hipStreamSynchronize(e->stream));
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+  mic_build_report_add("census", (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
+  if (c.stats[MIC_CENSUS_LOST])
+    rc = mic_set_error(MIC_E_INVALID, "table census: %llu k-mers are not found under their label", (unsigned long long)c.stats[MIC_CENSUS_LOST]);
+  else c.have = true;
+done:
+  if (rc) hipStreamSynchronize(e->stream);
+  if (d_bases) hipFree(d_bases);
+  return rc;
+}
+
 int build_from_device(mic_engine* e, const uint8_t* d_sizes_shard, uint64_t htsize, uint64_t s0, uint64_t s1,
                       const void* d_keys_shard, int key_bytes, const uint16_t* d_labels_shard, uint32_t sampling,
                       uint64_t rank_base) {
@@ -456,8 +490,10 @@ int build_from_device(mic_engine* e, const uint8_t* d_sizes_shard, uint64_t htsi
   fill_table(e, b, htsize, s0, s1, key_bytes, sampling, layout, m);
   { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
     mic_build_report_add("table build, total", (t.tv_sec - t_b0.tv_sec) + (t.tv_nsec - t_b0.tv_nsec) / 1e9); }
+  if (e->census.on) rc = run_census(e, d_sizes_shard, htsize, s0, s1, d_keys_shard, key_bytes, d_labels_shard, sampling, rank_base);
   // published in one piece: builds on other threads (mic_db_load_files_multi: one per device) neither wipe nor interleave it
   { std::lock_guard<std::mutex> lk(g_report_mu); g_report = t_report; }
+  if (rc) { const std::string why = g_err; mic_db_unload(e); return mic_set_error(rc, "%s", why.c_str()); }      // (the census refused the table)
   return MIC_OK;
 }
 
@@ -707,6 +743,7 @@ int mic_destroy(mic_engine* e) {
   if (e->rollup.d_counts) hipFree(e->rollup.d_counts);
   if (e->density.d_counts) hipFree(e->density.d_counts);
   if (e->ksketch.d_regs) hipFree(e->ksketch.d_regs);
+  if (e->census.d_counts) hipFree(e->census.d_counts);
   if (e->rollup.d_block) hipFree(e->rollup.d_block);
   if (e->ev0) mic_event_put(e->ev0);
   if (e->ev1) mic_event_put(e->ev1);
@@ -726,6 +763,8 @@ int mic_db_unload(mic_engine* e) {
   if (e->side) hipFree(e->side);
   if (e->d_sizes) hipFree(e->d_sizes);
   e->slots = nullptr; e->side = nullptr; e->d_sizes = nullptr; e->db_loaded = false;
+  if (e->census.d_counts) { hipFree(e->census.d_counts); e->census.d_counts = nullptr; }
+  e->census.have = false;
   memset(&e->info, 0, sizeof(e->info));
   return MIC_OK;
 }
@@ -769,6 +808,48 @@ int mic_db_set_part(mic_engine* e, uint32_t part, uint32_t n_parts) {
   if (n_parts > 65536) return mic_set_error(MIC_E_INVALID, "too many parts");
   if (e->db_loaded) return mic_set_error(MIC_E_STATE, "set the part before the database is loaded");
   e->part = n_parts > 1 ? part : 0; e->n_parts = n_parts > 1 ? n_parts : 0;
+  return MIC_OK;
+}
+
+int mic_db_census_enable(mic_engine* e, int on) {
+  if (!e) return mic_set_error(MIC_E_INVALID, "null engine");
+  if (e->db_loaded) return mic_set_error(MIC_E_STATE, "enable the census before the database is loaded");
+  e->census.on = on != 0;
+  return MIC_OK;
+}
+
+int mic_db_census_fetch(const mic_engine* e, uint64_t* counts, size_t n, uint64_t stats[8]) {
+  if (!e || !stats || (n && !counts)) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded || !e->census.have) return mic_set_error(MIC_E_STATE, "the table was loaded without mic_db_census_enable");
+  if (n != e->cfg.num_targets) return mic_set_error(MIC_E_INVALID, "%zu counts for %u targets", n, e->cfg.num_targets);
+  for (size_t t = 0; t < n; ++t) counts[t] = e->census.counts[t];
+  for (int f = 0; f < MIC_CENSUS_STATS; ++f) stats[f] = e->census.stats[f];
+  return MIC_OK;
+}
+
+int mic_db_census_device(mic_engine* e, const uint8_t* d_sizes, uint64_t htsize, const void* d_keys, int key_bytes, const uint16_t* d_labels,
+                         uint32_t sampling, uint64_t s0, uint64_t s1, uint64_t* d_counts, uint64_t* d_stats, void* stream) {
+  if (!e || !d_sizes || !d_keys || !d_labels || !d_stats || (e->cfg.num_targets && !d_counts)) return mic_set_error(MIC_E_INVALID, "null argument");
+  if (!e->db_loaded) return mic_set_error(MIC_E_STATE, "no database loaded");
+  if (htsize != e->info.htsize || key_bytes != (int)e->info.key_bytes)
+    return mic_set_error(MIC_E_INVALID, "the images (%llu buckets, %d-byte keys) are not the loaded table's (%llu, %u)", (unsigned long long)htsize,
+                         key_bytes, (unsigned long long)e->info.htsize, e->info.key_bytes);
+  int rc = set_device(e);
+  if (rc) return rc;
+  if ((rc = check_shard(htsize, s0, s1))) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  uint64_t base_elems = 0, base_rank = 0;
+  if (s0 > 0 && mic_reduce_sizes(d_sizes, s0, &base_elems, &base_rank, s) != 0) return mic_set_error(MIC_E_HIP, "size reduction failed");
+  void* d_bases = nullptr;
+  const int br = mic_tile_bases(d_sizes + s0, s1 - s0, &d_bases, s);
+  if (br) return mic_set_error(br == -3 ? MIC_E_NOMEM : MIC_E_HIP, "table census: the tile bases failed (%d)", br);
+  hipError_t he = mic_launch_census(e->table, e->slot_class, d_sizes + s0, s1 - s0, s0, htsize, (const char*)d_keys + base_elems * key_bytes, key_bytes,
+                                    d_labels + base_elems, d_bases, sampling, base_rank, e->cfg.num_targets, (unsigned long long*)d_counts,
+                                    (unsigned long long*)d_stats, s);
+  const hipError_t hs = hipStreamSynchronize(s);        // (the bases are this call's)
+  hipFree(d_bases);
+  if (he == hipSuccess) he = hs;
+  if (he != hipSuccess) return mic_set_error(MIC_E_HIP, "table census: %s", hipGetErrorString(he));
   return MIC_OK;
 }
 

@@ -535,6 +535,60 @@ long mic_ksketch_format(const char* const* names, const uint64_t* reads, const u
 }
 }  // extern "C"
 
+// ---- table census: the rule of mic_census.h on the CPU, and the coverage report as text ------------------------------------------------
+#include "mic_census.h"
+
+namespace {
+template <typename RAW>
+void census_host(const uint8_t* sizes, uint64_t htsize, const RAW* keys, const uint16_t* labels, uint32_t sampling, int k, uint32_t n_targets,
+                 uint64_t* counts, uint64_t* stats) {
+  uint64_t off = 0, rank = 0;
+  for (uint64_t b = 0; b < htsize; ++b) {
+    const uint32_t sz = sizes[b];
+    if (!sz) continue;
+    ++rank;                                                        // (the bucket's rank among the non-empty ones, counted from 1)
+    if (sampling <= 1 || rank % sampling == 0) {
+      MicCensusScan scan = mic_census_scan((uint64_t)keys[off + sz - 1]);
+      for (uint32_t e = 0; e < sz; ++e) {
+        const uint64_t kv = (uint64_t)keys[off + e];
+        if (!mic_census_reach(scan, kv)) continue;
+        const uint64_t c = kv * htsize + b;
+        if (!mic_census_is_canonical(c, k)) { ++stats[MIC_CENSUS_NONCANONICAL]; continue; }
+        const uint32_t l = (uint32_t)labels[off + e] + 1u;         // (no table to probe: found, under its file label)
+        ++stats[mic_census_field(l, true, labels[off + e])];
+        if (l <= n_targets) ++counts[l - 1]; else ++stats[MIC_CENSUS_BEYOND];
+      }
+    }
+    off += sz;
+  }
+}
+}  // namespace
+
+extern "C" {
+int mic_db_census_host(const uint8_t* sizes, uint64_t htsize, const void* keys, int key_bytes, const uint16_t* labels, uint32_t sampling, int k,
+                       uint32_t n_targets, uint64_t* counts, uint64_t stats[8]) {
+  if (k < 1 || k > 32 || !stats || (n_targets && !counts) || (htsize && !sizes)) return MIC_E_INVALID;
+  if (key_bytes != 2 && key_bytes != 4 && key_bytes != 8) return MIC_E_INVALID;
+  bool any = false;
+  for (uint64_t b = 0; b < htsize && !any; ++b) any = sizes[b] != 0;
+  if (any && (!keys || !labels)) return MIC_E_INVALID;
+  if (key_bytes == 8) census_host(sizes, htsize, (const uint64_t*)keys, labels, sampling, k, n_targets, counts, stats);
+  else if (key_bytes == 4) census_host(sizes, htsize, (const uint32_t*)keys, labels, sampling, k, n_targets, counts, stats);
+  else census_host(sizes, htsize, (const uint16_t*)keys, labels, sampling, k, n_targets, counts, stats);
+  return MIC_OK;
+}
+
+long mic_kcoverage_format(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, const uint64_t* target_kmers,
+                          uint32_t n_targets, char* buf, size_t cap) {
+  if (!names || !reads || !regs || !hits || !target_kmers) return MIC_E_INVALID;
+  for (uint32_t t = 0; t < n_targets; ++t) if (!names[t]) return MIC_E_INVALID;
+  std::string text;
+  if (!mic::ksketch::format_coverage(names, reads, regs, hits, target_kmers, n_targets, text)) return MIC_E_INVALID;
+  if (buf && text.size() < cap) memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
+}
+}  // extern "C"
+
 // ---- base-quality mask: the rule of mic_qmask.h on the CPU (batches the host path classifies, the host merge of paired files) ------
 #include "mic_qmask.h"
 

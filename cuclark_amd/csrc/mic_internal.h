@@ -292,6 +292,22 @@ hipError_t mic_line_starts(const uint8_t* raw, uint32_t nb, uint32_t from, const
                            hipStream_t s);
 hipError_t mic_text_warm(hipStream_t s);         // loads the device code of mic_text.hip (a no-op kernel of that file)
 
+// ---- table census (the kernel: mic_kernels.hip; the rule: mic_census.h; the engine's side: mic_engine.hip) -------------------------------
+// An engine's census while mic_db_census_enable is in force: allocated by the load that runs it (num_targets * 8 + 64 bytes on the
+// engine's device: the counts, then the 8 stats), freed by mic_db_unload / mic_destroy; mic_db_census_fetch reads the host copies.
+struct MicCensus {
+  bool on = false, have = false;          // enabled; the loaded table was counted
+  unsigned long long* d_counts = nullptr; // u64[n_targets], then u64[8]
+  std::vector<uint64_t> counts;
+  uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+// per 256-bucket tile of d_sizes the elements and the non-empty buckets in front of it (mic_build.hip: the builders' pass A), in a
+// device allocation the caller frees; 0, -1 (no or too many buckets), -3 (no memory), -4 (HIP error).  Synchronizes s.
+int mic_tile_bases(const uint8_t* d_sizes, uint64_t n_buckets, void** d_bases, hipStream_t s);
+hipError_t mic_launch_census(const MicTable& t, int slot_class, const uint8_t* d_sizes, uint64_t n_buckets, uint64_t bucket0, uint64_t htsize,
+                             const void* d_keys, int key_bytes, const uint16_t* d_labels, const void* bases, uint32_t sampling, uint64_t rank_base,
+                             uint32_t n_targets, unsigned long long* counts, unsigned long long* stats, hipStream_t s);
+
 // ---- read splitting (mic_split.hip; the rule: mic_split.h) --------------------------------------------------------------------------
 // An engine's setting while mic_split_start is in force: every ingest batch it owns that returns MIC_INGEST_OK is partitioned.
 struct MicSplit {

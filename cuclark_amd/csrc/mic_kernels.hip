@@ -14,6 +14,8 @@
 #include "mic_internal.h"
 #include "mic_device.h"
 #include "mic_ksketch.h"
+#include "mic_buckets.h"
+#include "mic_census.h"
 #include "mic_hitmap.h"
 #include "mic_join2.h"      // query_kernel_r: a read of two parts as one joined window, and its host model
 
@@ -2282,6 +2284,112 @@ __global__ void __launch_bounds__(256) ksketch_kernel(const MicTable t, const ui
   }
 }
 
+// ---- table census (mic_census.h: the rule): the database's own k-mers probed through the resident table, counted per target -------
+// On the load path, only when asked for.  A capped grid of 256-thread blocks strides over the 256-bucket tiles of the images; a thread
+// owns one bucket of the tile (the builders' walk, mic_buckets.h: the tile's bases, block_scan2 for the offsets inside it, the sampling
+// rule) and probes its reachable entries one after the other with probe_any at position 0: the lookup of a read that is exactly this
+// k-mer, on every layout, part and shard.
+//   counts     num_targets <= MIC_CENSUS_LDS_TARGETS: a histogram of u32 in dynamic LDS (4 B per target, at most 32 KiB), one LDS atomic
+//              per element, flushed as 64-bit global atomics (non-zero entries only) when the block is done - or after 65 536 tiles:
+//              a tile holds at most 256 x 255 elements, so no entry passes 65 536 x 65 280 < 2^32 between two flushes.
+//              above that: rounds over the wave's longest bucket (a trip count uniform in the wave), and per round the aggregation of
+//              ksketch_kernel's hit counters: per distinct label among the lanes one ballot, one popcount, one 64-bit atomic.
+//   stats      per thread in registers (a block sees fewer than 2^20 tiles x 255 per thread), summed per wave by shuffles, per block
+//              through LDS, then one atomic per block and non-zero field.
+// Plain loads, vector stores and atomics only.
+struct MicCensusArgs {
+  const uint8_t* sizes; uint64_t n_buckets; uint64_t bucket0; uint64_t htsize;
+  const void* keys; const uint16_t* labels; const TileA* bases;
+  uint64_t rank_base; uint32_t sampling, n_targets, n_tiles;
+};
+
+template <typename RAW, bool KEY64>
+__global__ void __launch_bounds__(TILE) census_kernel(const MicTable t, const MicCensusArgs a, unsigned long long* __restrict__ counts,
+                                                      unsigned long long* __restrict__ stats) {
+  extern __shared__ uint32_t census_hist[];                      // n_targets words on the LDS road, none on the other
+  __shared__ unsigned long long s_stats[TILE / 64][5];
+  const int lane = threadIdx.x & 63;
+  const bool in_lds = a.n_targets <= MIC_CENSUS_LDS_TARGETS;      // uniform in the grid
+  const int k = t.k;
+  uint32_t st[5] = {0, 0, 0, 0, 0};
+  uint32_t unflushed = 0;                                         // tiles counted into the histogram since its last flush
+  if (in_lds) {
+    for (uint32_t j = threadIdx.x; j < a.n_targets; j += TILE) census_hist[j] = 0;
+    __syncthreads();
+  }
+  for (uint32_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {      // uniform in the block: block_scan2 has barriers
+    const uint64_t i = (uint64_t)tile * TILE + threadIdx.x;
+    const uint32_t sz = i < a.n_buckets ? a.sizes[i] : 0;
+    uint32_t ea, eb, ta, tb;
+    block_scan2(sz, sz > 0, ea, eb, ta, tb);
+    const TileA base = a.bases[tile];
+    const uint32_t n = kept_bucket(sz, a.rank_base + base.nonzero + eb + 1, a.sampling) ? sz : 0;
+    const uint64_t off = base.elems + ea;
+    MicCensusScan scan = mic_census_scan(n ? raw_key<RAW>(a.keys, off + n - 1) : 0);
+    // one entry of this thread's bucket: 0, or label + 1 when it counts for a target
+    auto entry = [&](uint32_t e) -> uint32_t {
+      const uint64_t kv = raw_key<RAW>(a.keys, off + e);
+      if (!mic_census_reach(scan, kv)) return 0;
+      const uint64_t c = kv * a.htsize + (a.bucket0 + i);
+      if (!mic_census_is_canonical(c, k)) { ++st[MIC_CENSUS_NONCANONICAL]; return 0; }
+      bool mine = true;
+      const uint32_t l = probe_any<KEY64>(t, c, 0, &mine);
+      const int f = mic_census_field(l, mine, a.labels[off + e]);
+      ++st[f];
+      if (f != MIC_CENSUS_FOUND) return 0;
+      if (l > a.n_targets) { ++st[MIC_CENSUS_BEYOND]; return 0; }
+      return l;
+    };
+    if (in_lds) {
+      for (uint32_t e = 0; e < n; ++e) {
+        const uint32_t l = entry(e);
+        if (l) atomicAdd(&census_hist[l - 1], 1u);
+      }
+      if (++unflushed == 65536u) {
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < a.n_targets; j += TILE) {
+          const uint32_t v = census_hist[j];
+          if (v) { atomicAdd(&counts[j], (unsigned long long)v); census_hist[j] = 0; }
+        }
+        __syncthreads();
+        unflushed = 0;
+      }
+    } else {
+      uint32_t n_max = n;
+      for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(n_max, o); n_max = v > n_max ? v : n_max; }
+      for (uint32_t e = 0; e < n_max; ++e) {                       // uniform trip count: the ballots below see the whole wave
+        const uint32_t lab = e < n ? entry(e) : 0;
+        uint64_t mm = wballot(lab != 0);
+        while (mm) {
+          const uint32_t l1 = __builtin_amdgcn_readlane(lab, __builtin_ctzll(mm));
+          const uint64_t same = wballot(lab == l1);
+          mm &= ~same;
+          if (lane == __builtin_ctzll(same)) atomicAdd(&counts[l1 - 1], (unsigned long long)__builtin_popcountll(same));
+        }
+      }
+    }
+  }
+  if (in_lds) {
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < a.n_targets; j += TILE) {
+      const uint32_t v = census_hist[j];
+      if (v) atomicAdd(&counts[j], (unsigned long long)v);
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < 5; ++f) {
+    unsigned long long v = st[f];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if (lane == 0) s_stats[threadIdx.x >> 6][f] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    unsigned long long v = 0;
+    for (int w = 0; w < TILE / 64; ++w) v += s_stats[w][threadIdx.x];
+    if (v) atomicAdd(&stats[threadIdx.x], v);
+  }
+}
+
 // ---- hit maps (mic_hitmap.h: the rule): per read, the runs of equal labels along its k-mer positions ------------------------------
 // ksketch_kernel's shape: a scalar probe pass behind the query, one wavefront per read on a capped grid whose waves stride over the
 // batch, rounds of 64 positions with a trip count that is uniform in the wave.  Per round each lane probes its position and starts a
@@ -2399,6 +2507,27 @@ hipError_t mic_launch_ksketch(const MicTable& t, int slot_class, int n_cu, const
   if (blocks > cap) blocks = cap;
   if (slot_class == 64) ksketch_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, (uint32_t)n_reads, results, n_targets, regs, hits, status);
   else ksketch_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(t, reads_ptr, cont, (uint32_t)n_reads, results, n_targets, regs, hits, status);
+  return hipGetLastError();
+}
+
+// the census of the images' buckets [bucket0, bucket0 + n_buckets) against table t, ADDED to counts (u64[n_targets]) and stats (u64[8]);
+// bases: mic_tile_bases of d_sizes.  key_bytes is the images' and must be the table's (slot class 64 holds 8-byte keys, 32 the others).
+hipError_t mic_launch_census(const MicTable& t, int slot_class, const uint8_t* d_sizes, uint64_t n_buckets, uint64_t bucket0, uint64_t htsize,
+                             const void* d_keys, int key_bytes, const uint16_t* d_labels, const void* bases, uint32_t sampling, uint64_t rank_base,
+                             uint32_t n_targets, unsigned long long* counts, unsigned long long* stats, hipStream_t s) {
+  const uint64_t n_tiles = (n_buckets + TILE - 1) / TILE;
+  if (!n_tiles) return hipSuccess;
+  if (n_tiles > 0x7fffffffULL || (slot_class == 64) != (key_bytes == 8)) return hipErrorInvalidValue;
+  MicCensusArgs a;
+  a.sizes = d_sizes; a.n_buckets = n_buckets; a.bucket0 = bucket0; a.htsize = htsize; a.keys = d_keys; a.labels = d_labels;
+  a.bases = (const TileA*)bases; a.rank_base = rank_base; a.sampling = sampling; a.n_targets = n_targets; a.n_tiles = (uint32_t)n_tiles;
+  const unsigned blocks = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
+  const size_t lds = n_targets <= MIC_CENSUS_LDS_TARGETS ? (size_t)n_targets * 4 : 0;
+#define LAUNCH_CENSUS(RAW, K64) census_kernel<RAW, K64><<<blocks, TILE, lds, s>>>(t, a, counts, stats)
+  if (key_bytes == 8) LAUNCH_CENSUS(uint64_t, true);
+  else if (key_bytes == 4) LAUNCH_CENSUS(uint32_t, false);
+  else LAUNCH_CENSUS(uint16_t, false);
+#undef LAUNCH_CENSUS
   return hipGetLastError();
 }
 

@@ -84,6 +84,26 @@ class MiClarkDB:
         read*().  Super-k-mer layouts cut the resident table by slot range, the others by on-disk bucket range."""
         check(self.L.mic_db_set_part(self.h, int(part), int(n_parts)))
 
+    # -- table census (mic_db_census_*): counts u64[num_targets], stats u64[8] (csrc/mic_census.h)
+    def census_enable(self, on=True):
+        """Before read*(): the load then ends with the census of the table it built (a k-mer that does not come back under its label
+        fails the load)."""
+        check(self.L.mic_db_census_enable(self.h, int(bool(on))))
+
+    def census_fetch(self):
+        """(counts u64[num_targets], stats u64[8]) of the loaded table: the k-mers of every target in it, and
+        [found, answered elsewhere, not canonical, lost, found with a label at or above num_targets, 0, 0, 0]."""
+        counts = np.zeros(self.num_targets, np.uint64)
+        stats = np.zeros(8, np.uint64)
+        check(self.L.mic_db_census_fetch(self.h, counts.ctypes.data, counts.size, stats.ctypes.data))
+        return counts, stats
+
+    def census_device(self, d_sizes, htsize, d_keys, key_bytes, d_labels, d_counts, d_stats, sampling=1, shard=(0, 0), stream=0):
+        """The rule on caller-owned device images (whole) over the buckets of `shard` against the loaded table: ADDED to d_counts
+        (u64[num_targets]) and d_stats (u64[8]); waits for the stream."""
+        check(self.L.mic_db_census_device(self.h, d_sizes, int(htsize), d_keys, int(key_bytes), d_labels, int(sampling), int(shard[0]),
+                                          int(shard[1]), d_counts, d_stats, stream or None))
+
     def swapDbParts(self):
         """The table is fully resident: there is never another part to swap in (CuClarkDB.cu:813-858)."""
         return False

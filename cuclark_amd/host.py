@@ -304,6 +304,46 @@ def kraken_format(read_names, results, norm, k, offsets, words, target_names, fi
     return buf.raw[:ln]
 
 
+def db_census(sizes, keys, labels, k, n_targets, sampling=1):
+    """mic_db_census_host: the census rule of csrc/mic_census.h on the arrays a table is loaded from (bucket sizes u8[htsize], keys,
+    0-based labels), without a table: every canonical k-mer the builders enumerate counts under its file label - what a healthy whole
+    table returns.  Returns (counts u64[n_targets], stats u64[8])."""
+    L = _lib.load()
+    sz = np.ascontiguousarray(sizes, np.uint8).reshape(-1)
+    ky = np.ascontiguousarray(keys).reshape(-1)
+    lb = np.ascontiguousarray(labels, np.uint16).reshape(-1)
+    assert ky.dtype.itemsize in (2, 4, 8) and ky.dtype.kind == "u" and ky.size == lb.size
+    assert int(sz.sum(dtype=np.uint64)) == ky.size, "one key per element"
+    counts = np.zeros(int(n_targets), np.uint64)
+    stats = np.zeros(8, np.uint64)
+    rc = L.mic_db_census_host(sz.ctypes.data if sz.size else None, sz.size, ky.ctypes.data if ky.size else None, ky.dtype.itemsize,
+                              lb.ctypes.data if lb.size else None, int(sampling), int(k), int(n_targets),
+                              counts.ctypes.data if counts.size else None, stats.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"mic_db_census_host: invalid argument ({rc})")
+    return counts, stats
+
+
+def kcoverage_report(names, reads, regs, hits, target_kmers):
+    """mic_kcoverage_format: the report of exe/cuCLARK --kmer-coverage (csrc/kmer_report.hpp) as str: ksketch_report's arguments and
+    target_kmers, u64 per target (the census counts).  ValueError for a target with hits and no k-mers in the table."""
+    L = _lib.load()
+    n = len(names)
+    rd = np.ascontiguousarray(reads, np.uint64).reshape(-1)
+    rg = np.ascontiguousarray(regs, np.uint8).reshape(-1)
+    ht = np.ascontiguousarray(hits, np.uint64).reshape(-1)
+    tk = np.ascontiguousarray(target_kmers, np.uint64).reshape(-1)
+    assert rd.size == n and ht.size == n and tk.size == n and rg.size == n * _lib.MIC_KSKETCH_REGS
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else bytes(s) for s in names])
+    args = (C.cast(arr, C.c_void_p), rd.ctypes.data, rg.ctypes.data, ht.ctypes.data, tk.ctypes.data, n)
+    ln = L.mic_kcoverage_format(*args, None, 0)
+    if ln < 0:
+        raise ValueError(f"mic_kcoverage_format: invalid argument ({ln})")
+    buf = C.create_string_buffer(ln + 1)
+    assert L.mic_kcoverage_format(*args, buf, ln + 1) == ln
+    return buf.raw[:ln].decode()
+
+
 def rollup_check(n_targets, group_of):
     """mic_rollup_check: raises ValueError (with the library's message) unless group_of (u16[n_levels, n_targets], level 1 first) has
     1 .. 7 levels, ids numbered by first appearance at every level, and every level a coarsening of the one below."""

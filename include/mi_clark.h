@@ -615,6 +615,44 @@ double mic_ksketch_estimate(const uint8_t* regs_of_one_target);
 long mic_ksketch_format(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, uint32_t n_targets,
                         char* buf, size_t cap);
 
+/* ---- table census: the database's own k-mers probed through the resident table, counted per target (csrc/mic_census.h: the rule) ----
+ * mic_db_get_info has totals only; the census says how many k-mers of EACH target the resident table holds - the denominator of the
+ * coverage of exe/cuCLARK --kmer-coverage (distinct k-mers the reads touched / the target's k-mers in the table) - and checks the
+ * table while it counts.  The elements are those the table builders enumerate from the .sz / .ky / .lb images (kept buckets under
+ * `sampling`, entries the reference's scan reaches, c = key * htsize + bucket).  For each of them, with l = the lookup of a read that
+ * is exactly this k-mer (position 0) and `mine` = this engine answers for it:
+ *   stats[2]  c is not canonical (malformed databases only): nothing else happens
+ *   stats[1]  !mine: another part (mic_db_set_part) or shard answers for it
+ *   stats[0]  l == file label + 1; then counts[l - 1] += 1 when l <= num_targets, else stats[4] += 1 (in no counts entry)
+ *   stats[3]  lost: not found, or found under another label
+ * counts is u64[num_targets], stats u64[8] (stats[5 .. 7] are 0).  A healthy whole table shows stats[3] == 0, stats[0] ==
+ * mic_db_info.n_elems (a well-formed database) and sum(counts) == stats[0] - stats[4]; the parts' counts sum to the whole table's.
+ * mic_db_census_enable  before mic_db_load_*: the load then ends with the census (one kernel behind the build, while the images are
+ *                       still on the device; num_targets * 8 + 64 bytes of device memory until mic_db_unload; a "census: <seconds>"
+ *                       line in mic_db_last_build_report).  stats[3] != 0 fails the load with MIC_E_INVALID ("table census: N k-mers
+ *                       are not found under their label").  MIC_E_STATE once a table is loaded.  Off (the default): nothing is
+ *                       allocated or launched.
+ * mic_db_census_fetch   the loaded table's census from host copies; n == num_targets.  MIC_E_STATE when the table was loaded without
+ *                       mic_db_census_enable.
+ * mic_db_census_device  the rule on caller-owned device images (whole: d_sizes[htsize], the keys and labels of every bucket; the loaded
+ *                       table's htsize and key_bytes) over the buckets [s0, s1) (s1 == 0: htsize) against the loaded table; ADDS to
+ *                       d_counts (u64[num_targets]) and d_stats (u64[8]).  Runs on `stream` (NULL = the engine's) and waits for it.
+ * mic_db_census_host    the rule on the CPU (no device needed): the enumeration and the canonical test; there is no table to probe, so
+ *                       every canonical element counts under its file label - what a healthy whole table returns.  ADDS to counts
+ *                       (u64[n_targets]) and stats (u64[8]).
+ * mic_kcoverage_format  the report of exe/cuCLARK --kmer-coverage (csrc/kmer_report.hpp) as text: mic_ksketch_format's arguments and
+ *                       target_kmers (n_targets u64: the census counts).  Returns the length of the text (written with a terminator
+ *                       when it fits cap; buf may be NULL to ask for the length), or MIC_E_INVALID: a null argument, or a target with
+ *                       hits and no k-mers in the table (no healthy table gives one). */
+int mic_db_census_enable(mic_engine* e, int on);
+int mic_db_census_fetch(const mic_engine* e, uint64_t* counts, size_t n, uint64_t stats[8]);
+int mic_db_census_device(mic_engine* e, const uint8_t* d_sizes, uint64_t htsize, const void* d_keys, int key_bytes, const uint16_t* d_labels,
+                         uint32_t sampling, uint64_t s0, uint64_t s1, uint64_t* d_counts, uint64_t* d_stats, void* stream);
+int mic_db_census_host(const uint8_t* sizes, uint64_t htsize, const void* keys, int key_bytes, const uint16_t* labels, uint32_t sampling, int k,
+                       uint32_t n_targets, uint64_t* counts, uint64_t stats[8]);
+long mic_kcoverage_format(const char* const* names, const uint64_t* reads, const uint8_t* regs, const uint64_t* hits, const uint64_t* target_kmers,
+                          uint32_t n_targets, char* buf, size_t cap);
+
 /* ---- read splitting: the classified and the unclassified reads themselves, partitioned on the device (csrc/mic_split.h: the rule) ----
  * The reference says what every read is and cannot hand the reads back.  Record r of a text is the bytes from the first byte of its
  * header line up to the first byte of the next record's header line (the last record: to the end of the text); records are those of

@@ -215,6 +215,14 @@ int mic_ksketch_fetch(mic_engine*, uint8_t* regs, size_t n_regs, uint64_t* hits,
 }
 int mic_ksketch_stop(mic_engine*) { return MIC_OK; }
 int mic_batch_ksketch(mic_engine*, size_t) { return MIC_OK; }
+// table census: the mock builds no table; every target holds one k-mer, so that a coverage report can be written
+int mic_db_census_enable(mic_engine*, int) { return MIC_OK; }
+int mic_db_census_fetch(const mic_engine*, uint64_t* counts, size_t n, uint64_t stats[8]) {
+  for (size_t i = 0; i < n; ++i) counts[i] = 1;
+  for (int f = 0; f < 8; ++f) stats[f] = 0;
+  stats[0] = n;
+  return MIC_OK;
+}
 // roll-up counters: likewise (the host path's batches are counted by mic_rollup_host, which is mic_host.cpp's and under test)
 int mic_rollup_set(mic_engine*, uint32_t, const uint16_t*) { return MIC_OK; }
 int mic_rollup_start(mic_engine*, const mic_abund_filter*) { return MIC_OK; }
